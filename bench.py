@@ -10,6 +10,11 @@ persists across steps (steady state: every IP already known after warmup).
 
 Prints ONE JSON line on rank 0.  Multi-GPU: launched by torch.distributed.run,
 one rank per GPU.
+
+A plain run sets up, warms up, times --steps steps, writes the last step's
+outputs if --dump-outputs DIR is given, and prints the line.  --full adds what
+the headline value does not need: the cold steps, the steps re-timed with
+decision emission, the committed tail-inclusive figure and the CPU baseline.
 """
 import argparse
 import re
@@ -216,6 +221,39 @@ def tail_inclusive(workload):
             "what": "not measured in this run: the committed tools/tail_bench.py result on the same workload"}
 
 
+DUMP_MAX_BYTES = 60_000_000  # all files of one --dump-outputs together stay under 64 MB
+TRIP_FIELDS = ("line_idx", "line_offset", "line_len", "rule_idx", "ts_ns", "ip_off", "ip_len", "host_off", "host_len",
+               "rest_off", "decision")
+
+
+def dump_outputs(dirpath, o, compact, suffix=""):
+    """--dump-outputs: what the caller of the last timed step received (its
+    BatchOutput), as float64 .npy files under dirpath.  counts = (n_lines,
+    consumed_bytes, n_results, n_events, n_trips); trips = one row per trip in
+    the order the step returned them: (line byte offset, rule index) of the
+    compact words, or the TRIP_FIELDS of the full bjx_trip records.  The
+    values are integers below 2^53, which float64 holds exactly, but for ts_ns
+    (about 2^60.6: rounded to the nearest 256 ns, the same way on every run).
+    A trip list past DUMP_MAX_BYTES is cut to a fixed sample of its rows (seed
+    0, kept in order); trip_rows then holds the sampled row numbers."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    counts = np.array([o.n_lines, o.consumed_bytes, o.n_results, o.n_events, o.n_trips], dtype=np.float64)
+    np.save(os.path.join(dirpath, "counts%s.npy" % suffix), counts)
+    src = o.trips_compact() if compact else o.trips_array()
+    cols = 2 if compact else len(TRIP_FIELDS)
+    cap = DUMP_MAX_BYTES // (8 * (cols + 1))
+    if len(src) > cap:
+        rows = np.sort(np.random.default_rng(0).choice(len(src), cap, replace=False))
+        src = src[rows]
+        np.save(os.path.join(dirpath, "trip_rows%s.npy" % suffix), rows.astype(np.float64))
+    if compact:
+        trips = np.stack([src >> np.uint64(24), src & np.uint64(0xFFFFFF)], axis=1).astype(np.float64)
+    else:
+        trips = np.stack([src[f].astype(np.float64) for f in TRIP_FIELDS], axis=1)
+    np.save(os.path.join(dirpath, "trips%s.npy" % suffix), trips.reshape(len(src), cols))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -223,13 +261,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--lines", type=int, default=0, help="lines per GPU (default: workload size)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (counts and the trip list) "
+                         "as DIR/<name>.npy; the same arguments give the same inputs, so two builds compare file by file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline value does not need: the cold steps, "
+                         "the steps with decision emission (--bans-steps), the committed tail-inclusive figure and "
+                         "the CPU baseline (--cpu-sample, --no-cpu-baseline)")
     ap.add_argument("--cpu-sample", type=int, default=600_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--bans", type=int, default=0,
                     help="1: each step also emits the decision updates and ban-log lines of its trips on the device "
                          "(BJX_EMIT_BANS, copied to pinned host memory); 0: trip list only")
     ap.add_argument("--bans-steps", type=int, default=3,
-                    help="after the timed region, steps timed again with decision emission on (reported next to value)")
+                    help="--full: after the timed region, steps timed again with decision emission on (reported next "
+                         "to value)")
     ap.add_argument("--node-engines", type=int, default=0,
                     help="single process: one bjx_node of this many engines over the visible GPUs (round-robin), "
                          "e.g. to rehearse the N>1 node path on one GPU")
@@ -304,6 +350,7 @@ def main():
         ex = TorchExchange(torch.device("cuda", local))
 
     compact = args.trips == "compact"
+    bans_steps = args.bans_steps if args.full else 0  # the re-timed emission steps are part of --full
 
     def step():
         if node_mode:
@@ -320,11 +367,11 @@ def main():
         else:
             torch.cuda.synchronize()
 
-    # the first step goes into empty IP / state tables (every IP and (ip, rule
-    # name) state of the batch is new): timed on its own, with its phases
+    # --full: the first step goes into empty IP / state tables (every IP and
+    # (ip, rule name) state of the batch is new): timed on its own, with its phases
     cold = None
     for wi in range(args.warmup):
-        if wi == 0:
+        if wi == 0 and args.full:
             sync_all()
             tc0 = time.perf_counter()
             step()
@@ -348,32 +395,34 @@ def main():
     elapsed, outs = timed_region(dist, timed_step, sync_all, args.steps, "cuda")
     ms_per_step = elapsed * 1000.0 / args.steps
     if not drives:  # node mode, rank > 0: only the barriers and the max-over-ranks clock
-        if args.bans_steps > 0 and not bans:
-            timed_region(dist, step, sync_all, args.bans_steps, "cuda")
+        if bans_steps > 0 and not bans:
+            timed_region(dist, step, sync_all, bans_steps, "cuda")
         dist.barrier()
         dist.destroy_process_group()
         return
     match_ms = sum(o.match_kernel_ms for o in outs) / len(outs)
     dev_ms = sum(o.device_ms for o in outs) / len(outs)
     o = outs[-1]
+    if args.dump_outputs:  # before any later step reuses the engine's pinned output buffers
+        dump_outputs(args.dump_outputs, o, compact, "_rank%d" % rank if world > 1 else "")
     phases = eng.phase_ms()
     stats = eng.scan_stats()
     state_stats = node.state_stats() if node else eng.state_stats()
     # the same step with the Banner's work on the device too: per-IP decision
     # updates and every LogRegexBan line, copied to pinned host memory
     dec = None
-    if args.bans_steps > 0 and not bans:
+    if bans_steps > 0 and not bans:
         bans = True
         # untimed, as many steps as the plain run took: the emission's
         # first-use allocations (pinned host buffers grown to the largest
         # output of the steps' cycle: cfg5's trip count repeats every third
         # step, cfg3 has a trip burst every few dozen)
-        for _ in range(max(args.bans_steps, args.warmup + args.steps)):
+        for _ in range(max(bans_steps, args.warmup + args.steps)):
             step()
-        el2, _ = timed_region(dist, step, sync_all, args.bans_steps, "cuda")
+        el2, _ = timed_region(dist, step, sync_all, bans_steps, "cuda")
         bans = False
-        dec = {"value": round(n_lines * n_parts / (el2 / args.bans_steps), 1), "unit": "lines/s",
-               "ms_per_step": round(el2 * 1000.0 / args.bans_steps, 3), "steps": args.bans_steps,
+        dec = {"value": round(n_lines * n_parts / (el2 / bans_steps), 1), "unit": "lines/s",
+               "ms_per_step": round(el2 * 1000.0 / bans_steps, 3), "steps": bans_steps,
                "what": "each step also builds the per-IP DynamicDecisionLists updates and all LogRegexBan JSON lines "
                        "on the device and copies them to pinned host memory (BJX_EMIT_BANS)"}
         if not node_mode and not dist and ex is None:
@@ -393,7 +442,7 @@ def main():
                 dec["host_apply"] = {
                     "ms": round(secs * 1000.0, 3), "records": int(bb.n_ips), "entries_changed": int(changed),
                     "log_bytes": int(bb.log_bytes),
-                    "step_plus_host_lines_per_s": round(n_lines / (el2 / args.bans_steps + secs), 1),
+                    "step_plus_host_lines_per_s": round(n_lines / (el2 / bans_steps + secs), 1),
                     "what": "one step's per-IP records applied by a compiled stand-in for the Go host "
                             "(DynamicDecisionLists.Update into an empty open-addressing map keyed by the IP "
                             "bytes, decision.go:404-439) and its LogRegexBan lines appended to a file in /tmp "
@@ -402,24 +451,24 @@ def main():
     # the decision records alone (BJX_BAN_RECORDS_ONLY: no LogRegexBan lines
     # built or copied), single-engine runs
     rec = None
-    if args.bans_steps > 0 and not args.bans and ex is None and not node_mode and not dist:
-        for _ in range(args.bans_steps):  # untimed, as above
+    if bans_steps > 0 and not args.bans and ex is None and not node_mode and not dist:
+        for _ in range(bans_steps):  # untimed, as above
             eng.process(rs, None, now, device_ptr=data.data_ptr(), nbytes=nbytes, emit_bans=True, ban_log=False)
         sync_all()
         t2 = time.perf_counter()
-        for _ in range(args.bans_steps):
+        for _ in range(bans_steps):
             eng.process(rs, None, now, device_ptr=data.data_ptr(), nbytes=nbytes, emit_bans=True, ban_log=False)
         sync_all()
         el3 = time.perf_counter() - t2
-        rec = {"value": round(n_lines / (el3 / args.bans_steps), 1), "unit": "lines/s",
-               "ms_per_step": round(el3 * 1000.0 / args.bans_steps, 3), "steps": args.bans_steps,
+        rec = {"value": round(n_lines / (el3 / bans_steps), 1), "unit": "lines/s",
+               "ms_per_step": round(el3 * 1000.0 / bans_steps, 3), "steps": bans_steps,
                "what": "each step also builds the per-IP DynamicDecisionLists updates on the device and copies them "
                        "to pinned host memory, without the LogRegexBan lines (BJX_EMIT_BANS | BJX_BAN_RECORDS_ONLY)"}
     # empty tables again, workspace warm: one step that creates every IP and
     # state of the batch (the new-IP path without the engine's first
     # allocations), single-engine runs
     cold_clear = None
-    if not node_mode and not dist and ex is None:
+    if args.full and not node_mode and not dist and ex is None:
         eng.state_clear()
         sync_all()
         tcc = time.perf_counter()
@@ -490,10 +539,10 @@ def main():
             line["with_decision_emission"] = dec
         if rec:
             line["with_decision_records_only"] = rec
-        tail = tail_inclusive(w0.name) if n_parts == 1 else None
+        tail = tail_inclusive(w0.name) if args.full and n_parts == 1 else None
         if tail:
             line["tail_inclusive"] = tail
-        if not args.no_cpu_baseline and n_parts == 1:
+        if args.full and not args.no_cpu_baseline and n_parts == 1:
             line["cpu_baseline"] = cpu_baseline(w, args.cpu_sample)
         print(json.dumps(line), flush=True)
     if dist:

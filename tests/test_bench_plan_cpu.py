@@ -68,6 +68,48 @@ def test_rank_plan_single_process_gpus8():
     assert p["devices"] == list(range(8)) and p["drives"]
 
 
+class _Out:
+    """A BatchOutput stand-in: counts plus compact trip words."""
+
+    def __init__(self, words):
+        self.n_lines, self.consumed_bytes, self.n_results, self.n_events = 1000, 150_000, 1500, 1400
+        self.n_trips = len(words)
+        self._w = words
+
+    def trips_compact(self):
+        return self._w
+
+
+def test_dump_outputs_compact_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float64 counts and one (line offset, rule index) row per
+    trip, in order; a list past the size cap becomes the same sample of rows
+    on every run, with the row numbers beside it."""
+    import numpy as np
+    offs = np.arange(50, dtype=np.uint64) * np.uint64(153) + np.uint64(1 << 33)  # offsets past 2^32 survive
+    rules = np.arange(50, dtype=np.uint64) % np.uint64(7)
+    o = _Out((offs << np.uint64(24)) | rules)
+    d = str(tmp_path / "a")
+    bench.dump_outputs(d, o, True)
+    assert sorted(os.listdir(d)) == ["counts.npy", "trips.npy"]
+    counts, trips = np.load(os.path.join(d, "counts.npy")), np.load(os.path.join(d, "trips.npy"))
+    assert counts.dtype == trips.dtype == np.float64
+    assert counts.tolist() == [1000, 150_000, 1500, 1400, 50]
+    assert trips.shape == (50, 2) and (trips[:, 0] == offs).all() and (trips[:, 1] == rules).all()
+    # no trips: an empty (0, 2) array, not a missing file
+    bench.dump_outputs(str(tmp_path / "e"), _Out(np.zeros(0, dtype=np.uint64)), True)
+    assert np.load(str(tmp_path / "e" / "trips.npy")).shape == (0, 2)
+    # past the cap: 10 of the 50 rows, the same ones each time, in order
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * 8 * 3)
+    got = []
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), o, True)
+        rows = np.load(str(tmp_path / name / "trip_rows.npy"))
+        t = np.load(str(tmp_path / name / "trips.npy"))
+        assert t.shape == (10, 2) and (np.diff(rows) > 0).all() and (t[:, 0] == offs[rows.astype(int)]).all()
+        got.append(rows.tolist())
+    assert got[0] == got[1]
+
+
 class _Counted:
     """torch.distributed with its collectives counted (in call order)."""
 
