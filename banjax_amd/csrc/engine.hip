@@ -573,6 +573,7 @@ constexpr uint32_t kHitSlots = 4;     // verified literal hits kept per line
 constexpr int kScanWaves = 16;        // waves per block (one block per CU)
 constexpr uint32_t kTileLds = kWT + kHalo + 16;
 constexpr uint32_t kWaveJobs = 64;   // DFA jobs staged per wave before one global append
+constexpr int kScanGroup = 8;         // pair entries read from LDS together in k_scan's filter (4 and 16 time the same: DESIGN §4q)
 constexpr uint32_t kCandList = 128;   // candidate positions verified per round (one per lane)
 constexpr uint32_t kBanChunks = 8;                  // ban-log write/copy chunks of a batch (emit_bans)
 constexpr uint64_t kBanChunkMin = 64ull << 20;     // logs up to this size go in one chunk
@@ -690,7 +691,7 @@ struct ScanArgs {
   uint64_t *nl;
   Lines L;
   unsigned long long *stats;  // [0] bitset hits, [1] recorded literal hits
-  uint32_t shared_bytes;      // per-wave LDS regions start here
+  uint32_t shared_bytes;      // per-wave LDS regions start here (offset in the dynamic segment)
   uint32_t debug_skip;        // timing experiments only (BJX_DEBUG_SKIP, results invalid): 1 gram phase, 2 candidates,
                               // 4 literal checks of gram table hits, 8 gram table probes
 };
@@ -1623,11 +1624,14 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) {
 template <bool IMG_LDS>
 __global__ __launch_bounds__(kScanWaves * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_scan(Bind B, ScanArgs A) {
   // ---- block-shared tables (read-only after this barrier): the gram pair
-  // table, then the scan's lookup image when it fits
-  uint8_t *s_bits = s_dyn;
-  uint8_t *s_img = s_dyn + kPairBytes;
+  // table, then the scan's lookup image when it fits.  The pair table is the
+  // kernel's only static LDS, so its address is a compile-time constant that
+  // folds into the probes' ds_read_b64 (off the dynamic segment's symbol every
+  // entry address paid a v_add of the base); the dynamic segment follows it.
+  __shared__ __attribute__((aligned(16))) uint2 s_pairs[kPairEntries];
+  uint8_t *s_img = s_dyn;
   for (uint32_t i = threadIdx.x; i < kPairBytes / 16; i += blockDim.x)
-    reinterpret_cast<uint4 *>(s_bits)[i] = reinterpret_cast<const uint4 *>(B.gram_pairs)[i];
+    reinterpret_cast<uint4 *>(s_pairs)[i] = reinterpret_cast<const uint4 *>(B.gram_pairs)[i];
   if (IMG_LDS)
     for (uint32_t i = threadIdx.x; i < B.scan_img_bytes / 16; i += blockDim.x)
       reinterpret_cast<uint4 *>(s_img)[i] = reinterpret_cast<const uint4 *>(B.scan_img)[i];
@@ -1635,7 +1639,10 @@ __global__ __launch_bounds__(kScanWaves * 64) __attribute__((amdgpu_waves_per_eu
   const Tabs TB = make_tabs(IMG_LDS ? s_img : B.scan_img, B.sil);
   const uint32_t *gt = TB.gt, *ge = TB.ge;
 
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // the wave index through readfirstlane: the compiler cannot prove it uniform,
+  // and the tile index, its byte and line bases and every test on them then
+  // stay on the scalar unit
+  const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   uint8_t *T = s_dyn + A.shared_bytes + wave * kWaveLds;
   uint16_t *ls = reinterpret_cast<uint16_t *>(T + kTileLds);
   uint16_t *le = ls + kLineCap;
@@ -1648,7 +1655,7 @@ __global__ __launch_bounds__(kScanWaves * 64) __attribute__((amdgpu_waves_per_eu
   uint32_t n_probe = 0, n_hit = 0, n_gram = 0;
 
   const uint64_t nw = (uint64_t)gridDim.x * kScanWaves;
-  uint64_t t = (uint64_t)blockIdx.x * kScanWaves + wave;
+  const uint64_t t_first = (uint64_t)blockIdx.x * kScanWaves + wave;
   // Everything a tile needs from HBM is loaded one tile ahead, together: its
   // 64 B per lane, its halo (8 B per lane), and in `qa` the word before the
   // tile (lane 0) and the tile's first line indices tile_base[t] (lanes 1-2)
@@ -1657,11 +1664,11 @@ __global__ __launch_bounds__(kScanWaves * 64) __attribute__((amdgpu_waves_per_eu
   // after the prefetch: the loop body reads only LDS and registers, and the
   // long-line hits that need a slot index from HBM wait at the end of a round
   // (flush_long), when the prefetch has had the whole tile to arrive.
-  uint4 q[4];
-  uint2 qh;
-  uint32_t qa;
-  auto load_tile = [&](uint64_t tt) {
-    const uint64_t ts = tt * kWT, base = ts + lane * 64u;
+  uint4 q[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+  uint2 qh = make_uint2(0, 0);
+  uint32_t qa = 0;
+  // a tile whose window reaches the batch end: bytes past it read as 0
+  auto load_tile_edge = [&](uint64_t ts, uint64_t base) __attribute__((always_inline)) {
     if (base + 64 <= A.n) {
       const uint4 *src = reinterpret_cast<const uint4 *>(A.buf + base);
 #pragma unroll
@@ -1695,6 +1702,21 @@ __global__ __launch_bounds__(kScanWaves * 64) __attribute__((amdgpu_waves_per_eu
         if (k < 4) a |= byte << (8 * k); else b |= byte << (8 * (k - 4));
       }
       qh = make_uint2(a, b);
+    }
+  };
+  auto load_tile = [&](uint64_t tt) __attribute__((always_inline)) {
+    const uint64_t ts = tt * kWT, base = ts + lane * 64u;
+    // tile and halo wholly inside the batch (every tile but the last one or
+    // two): one scalar test, no per-lane bounds; the byte-wise loaders
+    // (load_tile_edge) are the cold side of that branch, outside the loop's code
+    const bool full = ts + kWT + kHalo <= A.n;
+    if (__builtin_expect(full, 1)) {
+      const uint4 *src = reinterpret_cast<const uint4 *>(A.buf + base);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) q[k] = src[k];
+      qh = *reinterpret_cast<const uint2 *>(A.buf + ts + kWT + lane * 8u);
+    } else {
+      load_tile_edge(ts, base);
     }
     qa = 0x0A000000u;  // before the batch: as if after a '\n'
     if (lane == 0) {
@@ -1742,20 +1764,35 @@ __global__ __launch_bounds__(kScanWaves * 64) __attribute__((amdgpu_waves_per_eu
     wave_sync();
   };
 
-  const uint64_t n_iter = (A.n_tiles + nw - 1) / nw;
-  if (t < A.n_tiles) load_tile(t);
-  for (uint32_t r = 0; r < n_iter; ++r, t += nw) {
-    if (t >= A.n_tiles) continue;
-    const uint64_t ts0 = t * kWT;
-    uint32_t w[16];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { w[4 * k] = q[k].x; w[4 * k + 1] = q[k].y; w[4 * k + 2] = q[k].z; w[4 * k + 3] = q[k].w; }
+  // One trip loads tile tl and processes the tile loaded the trip before (the
+  // first trip only loads): load_tile has this one call site, so the edge
+  // loaders are in the kernel's code once, and always_inline keeps them from
+  // becoming a call (a called lambda's captures, q and A included, would live
+  // in scratch).
+  bool have = false;
+  uint64_t tc = 0;
+  for (uint64_t tl = t_first;; tl += nw) {
+    const bool more = tl < A.n_tiles;
+    if (!have && !more) break;
+    const uint4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
     const uint2 hv = qh;
-    const uint32_t prevb = (uint32_t)__builtin_amdgcn_readlane(qa, 0) >> 24;
-    const uint64_t tb = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(qa, 1) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(qa, 2) << 32);
-    const uint64_t tbm = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(qa, 3) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(qa, 4) << 32);
+    const uint32_t qa0 = qa;
+    if (more) load_tile(tl);  // prefetch
+    const bool cur = have;
+    const uint64_t t = tc;
+    have = more;
+    tc = tl;
+    if (!cur) continue;
+    const uint64_t ts0 = t * kWT;
+    // edge tile: the first, the last, or one whose window (tile + halo) reaches
+    // the batch end.  Only these compare positions with A.n; an interior tile's
+    // bytes are all inside the batch.
+    const bool edge = t == 0 || t + 1 >= A.n_tiles || ts0 + kWT + kHalo > A.n;
+    const uint32_t w[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
+    const uint32_t prevb = (uint32_t)__builtin_amdgcn_readlane(qa0, 0) >> 24;
+    const uint64_t tb = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(qa0, 1) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(qa0, 2) << 32);
+    const uint64_t tbm = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(qa0, 3) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(qa0, 4) << 32);
     const uint32_t prev_cnt = t ? (uint32_t)(tb - tbm) : 0u;
-    if (t + nw < A.n_tiles) load_tile(t + nw);  // prefetch
     uint4 *dst = reinterpret_cast<uint4 *>(T + lane * 64u);
 #pragma unroll
     for (int k = 0; k < 4; ++k) dst[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
@@ -1800,7 +1837,7 @@ __global__ __launch_bounds__(kScanWaves * 64) __attribute__((amdgpu_waves_per_eu
       hmask = ((a >> 7) & 1u) | ((a >> 14) & 2u) | ((a >> 21) & 4u) | ((a >> 28) & 8u) |
               (((b >> 7) & 1u) | ((b >> 14) & 2u) | ((b >> 21) & 4u) | ((b >> 28) & 8u)) << 4;
     }
-    if (ts0 + kWT + lane * 8u >= A.n) hmask = 0;
+    if (edge && ts0 + kWT + lane * 8u >= A.n) hmask = 0;
     const uint64_t any_h = __ballot(hmask != 0);
     uint32_t hfirst = kNone;
     if (any_h) {
@@ -1808,14 +1845,21 @@ __global__ __launch_bounds__(kScanWaves * 64) __attribute__((amdgpu_waves_per_eu
       hfirst = kWT + fl * 8u + (uint32_t)__ffs(__shfl(hmask, fl)) - 1;
     }
     // ---- nl[] and the positions of lines starting in this tile (tile-relative)
+    // (tile-relative 32-bit values in the loop; the 64-bit bases once per tile:
+    // nl_t and the room left in nl[] are scalar, ts0 is a multiple of the tile
+    // size so ts0 + p is an or into its low word)
     {
       uint64_t x = nlm;
       uint32_t rr = pre;
+      uint2 *nl_t = reinterpret_cast<uint2 *>(A.nl + tb);
+      const uint64_t room64 = tb < A.n_lines ? A.n_lines - tb : 0;
+      const uint32_t room = room64 < (uint64_t)kWT ? (uint32_t)room64 : kWT;  // a tile has at most kWT '\n'
+      const uint32_t ts_lo = (uint32_t)ts0, ts_hi = (uint32_t)(ts0 >> 32);
       while (x) {
         const uint32_t b = (uint32_t)__ffsll((unsigned long long)x) - 1;
         x &= x - 1;
         const uint32_t p = lane * 64u + b;
-        if (tb + rr < A.n_lines) A.nl[tb + rr] = ts0 + p;
+        if (rr < room) nl_t[rr] = make_uint2(ts_lo | p, ts_hi);
         const int32_t lk = (int32_t)rr - (int32_t)nh;  // started line this '\n' ends
         if (lk >= 0 && lk < (int32_t)kLineCap) le[lk] = (uint16_t)p;
         if (p + 1 < kWT && lk + 1 < (int32_t)kLineCap) ls[lk + 1] = (uint16_t)(p + 1);
@@ -1842,35 +1886,47 @@ __global__ __launch_bounds__(kScanWaves * 64) __attribute__((amdgpu_waves_per_eu
     // k + 1 .. k + 3), its low word holding bit (byte k & 31) for the gram at
     // k, its high word bit (byte k + 4 & 31) for the gram at k + 1
     // (engine_types.h gram_pair_*).  Eight entry addresses, then their eight
-    // ds_read_b64 in flight together, then the bits: per pair one or two
-    // alignbytes, a 24-bit mul, a shift and an and (the address), two bfe (the
-    // bfe offsets take the bytes' low 5 bits as they are), a shift, two
-    // shift-ors
+    // ds_read_b64 in flight together, then the bits.  Per pair: one or two
+    // alignbytes (the grams at k + 1 and, off a word boundary, at k), the
+    // 24-bit mul, a shift and an and (the address), and per result bit a shift
+    // of the entry word by the byte as it is (the shifter reads its low 5 bits)
+    // and one alignbit that rotates bit 0 into the top of the mask, so 32
+    // results in position order leave the first at bit 0.  Byte k + 4 is the
+    // low byte of the gram at k + 4, which the pair two further on needs anyway
+    // (past the lane's last word: the next lane's first word, nxt).
     {
       const uint32_t nxt = *reinterpret_cast<const uint32_t *>(T + lane * 64u + 64u);
+      // the gram at even offset k of words wd[] (k a compile-time constant)
+      auto gram_at = [](const uint32_t *wd, int k) -> uint32_t {
+        return (k & 3) ? __builtin_amdgcn_alignbyte(wd[(k >> 2) + 1], wd[k >> 2], (uint32_t)(k & 3)) : wd[k >> 2];
+      };
+      auto push_bit = [](uint32_t acc, uint32_t word, uint32_t byte) -> uint32_t {
+        return __builtin_amdgcn_alignbit(word >> (byte & 31u), acc, 1u);
+      };
+      uint32_t wx[17];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) wx[k] = w[k];
+      wx[16] = nxt;
       uint32_t hlo = 0, hhi = 0;
 #pragma unroll
-      for (int k0 = 0; k0 < 64; k0 += 16) {
-        uint2 ent[8];
+      for (int k0 = 0; k0 < 64; k0 += 2 * kScanGroup) {
+        uint2 ent[kScanGroup];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < kScanGroup; ++i) {
           const int k = k0 + 2 * i;
-          const uint32_t lo = w[k >> 2], hi = (k >> 2) < 15 ? w[(k >> 2) + 1] : nxt;
-          const uint32_t g1 = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(k & 3) + 1u);  // bytes k + 1 .. k + 4
-          ent[i] = *reinterpret_cast<const uint2 *>(s_bits + gram_pair_byte_off(g1));
+          const uint32_t g1 = __builtin_amdgcn_alignbyte(wx[(k >> 2) + 1], wx[k >> 2], (uint32_t)(k & 3) + 1u);  // bytes k + 1 .. k + 4
+          ent[i] = s_pairs[gram_pair_byte_off(g1) >> 3];
         }
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < kScanGroup; ++i) {
           const int k = k0 + 2 * i;
-          const uint32_t lo = w[k >> 2], hi = (k >> 2) < 15 ? w[(k >> 2) + 1] : nxt;
-          const uint32_t g0 = (k & 3) ? __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(k & 3)) : lo;  // bytes k .. k + 3
-          const uint32_t g1 = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(k & 3) + 1u);
-          const uint32_t two = __builtin_amdgcn_ubfe(ent[i].x, g0, 1) | (__builtin_amdgcn_ubfe(ent[i].y, g1 >> 24, 1) << 1);
-          if (k < 32) hlo |= two << k; else hhi |= two << (k - 32);
+          const uint32_t b4 = k + 4 <= 64 ? gram_at(wx, k + 4) : nxt >> 16;  // low byte: byte k + 4
+          if (k < 32) hlo = push_bit(push_bit(hlo, ent[i].x, gram_at(wx, k)), ent[i].y, b4);
+          else hhi = push_bit(push_bit(hhi, ent[i].x, gram_at(wx, k)), ent[i].y, b4);
         }
       }
       uint64_t hits = ((uint64_t)hhi << 32) | hlo;
-      if (ts0 + lane * 64u + 64u > A.n) hits &= (ts0 + lane * 64u >= A.n) ? 0ull : ((1ull << (A.n - ts0 - lane * 64u)) - 1ull);
+      if (edge && ts0 + lane * 64u + 64u > A.n) hits &= (ts0 + lane * 64u >= A.n) ? 0ull : ((1ull << (A.n - ts0 - lane * 64u)) - 1ull);
       // halo positions of the last started line: the lane's 8 halo bytes (hv)
       // and the next lane's first 4, as four pairs with their reads in flight
       uint32_t hh = 0;
@@ -1881,16 +1937,15 @@ __global__ __launch_bounds__(kScanWaves * 64) __attribute__((amdgpu_waves_per_eu
         for (int i = 0; i < 4; ++i) {
           const int k = 2 * i;
           const uint32_t g1 = __builtin_amdgcn_alignbyte(hw[(k >> 2) + 1], hw[k >> 2], (uint32_t)(k & 3) + 1u);
-          ent[i] = *reinterpret_cast<const uint2 *>(s_bits + gram_pair_byte_off(g1));
+          ent[i] = s_pairs[gram_pair_byte_off(g1) >> 3];
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int k = 2 * i;
-          const uint32_t lo = hw[k >> 2], hi = hw[(k >> 2) + 1];
-          const uint32_t g0 = (k & 3) ? __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(k & 3)) : lo;
-          const uint32_t g1 = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(k & 3) + 1u);
-          hh |= (__builtin_amdgcn_ubfe(ent[i].x, g0, 1) | (__builtin_amdgcn_ubfe(ent[i].y, g1 >> 24, 1) << 1)) << k;
+          const uint32_t b4 = k + 4 <= 8 ? gram_at(hw, k + 4) : hw[2] >> 16;
+          hh = push_bit(push_bit(hh, ent[i].x, gram_at(hw, k)), ent[i].y, b4);
         }
+        hh >>= 24;  // 8 results: the first at bit 0
         const uint32_t nv = hend - (kWT + lane * 8u);  // halo positions before hend
         if (nv < 8) hh &= (1u << nv) - 1u;
       }
@@ -7231,10 +7286,11 @@ static bool match_phase(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *byt
     A.buf = buf; A.n = n; A.n_tiles = n_tiles; A.n_lines = cap; A.tile_base = e->tile_base.p; A.nl = e->nl.p;
     A.L = L; A.stats = e->scalars.p + 8;
     A.debug_skip = getenv("BJX_DEBUG_SKIP") ? (uint32_t)atoi(getenv("BJX_DEBUG_SKIP")) : 0u;
-    // block-shared LDS: the gram pair table, the scan's lookup image when it fits, then 16 wave regions
+    // block-shared LDS: the gram pair table (static in the kernel), then in the dynamic segment the
+    // scan's lookup image when it fits and the 16 wave regions
     const uint32_t fixed = kPairBytes + kScanWaves * kWaveLds;
     const bool img_lds = fixed + B.scan_img_bytes <= kScanLdsMax;
-    A.shared_bytes = kPairBytes + (img_lds ? B.scan_img_bytes : 0);
+    A.shared_bytes = img_lds ? B.scan_img_bytes : 0;
     const uint32_t lds = A.shared_bytes + kScanWaves * kWaveLds;
     using ScanFn = void (*)(Bind, ScanArgs);
     const ScanFn kfn = img_lds ? k_scan<true> : k_scan<false>;

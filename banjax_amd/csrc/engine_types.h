@@ -47,16 +47,21 @@ constexpr uint32_t kJiNfa = 1, kJiEquiv = 2, kJiBigLit = 16;  // bits 2-3: lead 
 // k + 1 bit (its last byte & 31) of the high word.  A registered gram sets its
 // bit in both roles (the entry of its last three bytes, low word; the entry of
 // its first three bytes, high word), so no occurrence is missed at either
-// parity.  gram_mix: the low 32 bits of a 24 x 24-bit product (one full-rate
-// v_mul_u32_u24 on the device; only the key's low 24 bits count); its bits
-// 13..23 pick the entry.  (Bits 34..44 of the full product spread cfg2's
-// similar host literals worse: k_scan 17.5 -> 32 ms, round 4.)
+// parity.  gram_mix: the low 32 bits of a 24 x 24-bit product (only the key's
+// low 24 bits count); its bits 13..23 pick the entry.  On the device it is
+// one full-rate v_mul_u32_u24, written as asm: from __umul24 the compiler
+// emits v_mul_lo_u32 (only product bits 13..23 are demanded, so the 24-bit
+// masks fold away and the 24-bit form is never selected).  (Bits 34..44 of
+// the full product spread cfg2's similar host literals worse: k_scan
+// 17.5 -> 32 ms, round 4.)
 constexpr uint32_t kPairEntries = 2048;
 constexpr uint32_t kPairBytes = kPairEntries * 8;
 constexpr uint32_t kGramMul = 0x2C1B3Bu;
 __host__ __device__ inline uint32_t gram_mix(uint32_t x) {
 #ifdef __HIP_DEVICE_COMPILE__
-  return __umul24(x, kGramMul);
+  uint32_t m;
+  asm("v_mul_u32_u24 %0, %1, %2" : "=v"(m) : "s"(kGramMul), "v"(x));
+  return m;
 #else
   return (x & 0xFFFFFFu) * kGramMul;
 #endif
