@@ -107,13 +107,21 @@ EXPORTS = [
     "bjx_node_create", "bjx_node_destroy", "bjx_node_size", "bjx_node_engine", "bjx_node_last_error", "bjx_node_set_decision_lists",
     "bjx_node_set_ban_options", "bjx_node_process_batch", "bjx_node_process_chunks", "bjx_node_batch_bans",
     "bjx_node_state_get", "bjx_node_state_len", "bjx_node_state_dump", "bjx_node_state_stats_get",
-    "bjx_node_state_clear", "bjx_node_exchange_kind",
+    "bjx_node_state_clear", "bjx_node_exchange_kind", "bjx_state_expire", "bjx_node_state_expire",
 ]
 
 
 class StateStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("ips", "ip_slots", "states", "state_slots", "arena_bytes", "arena_capacity",
                                             "device_bytes", "rehashes")]
+
+
+class ExpireStats(C.Structure):
+    """bjx_expire_stats: what one bjx_state_expire dropped and freed."""
+    _fields_ = [(k, C.c_uint64) for k in ("states_before", "states_dropped", "ips_before", "ips_dropped",
+                                            "arena_bytes_before", "arena_bytes_after", "device_bytes_before",
+                                            "device_bytes_after")] + [("device_ms", C.c_double)]
+
 
 _lib = None
 
@@ -252,6 +260,10 @@ def lib():
     L.bjx_node_state_stats_get.argtypes = [vp, C.c_void_p]
     L.bjx_node_state_clear.restype = C.c_int
     L.bjx_node_state_clear.argtypes = [vp]
+    L.bjx_state_expire.restype = C.c_int
+    L.bjx_state_expire.argtypes = [vp, C.c_int64, C.POINTER(ExpireStats)]
+    L.bjx_node_state_expire.restype = C.c_int
+    L.bjx_node_state_expire.argtypes = [vp, C.c_int64, C.POINTER(ExpireStats)]
     _lib = L
     return L
 

@@ -4350,6 +4350,87 @@ __global__ void k_rehash_st(uint64_t old_cap, const StSlot *__restrict__ o, StSl
   }
 }
 
+// expiry (bjx_state_expire): a rebuild into fresh tables that drops every
+// state whose window started before the cutoff and every IP left without one.
+// IP ids stay dense and in first-seen order: keep[id] marks the IPs with a
+// surviving state, its exclusive scan is the new id, the scan of the kept
+// lengths the new arena offset.
+__device__ __forceinline__ bool st_survives(const StSlot &v, int64_t cutoff, uint64_t n_ips) {
+  // (an id past n_ips cannot come from a finished batch: never followed)
+  return v.key != 0 && v.valid != 0 && v.start >= cutoff && (v.key >> 24) - 1 < n_ips;
+}
+// grid-stride; cnt[0] += surviving states (one atomic per block)
+__global__ __launch_bounds__(kBlock) void k_exp_mark(uint64_t st_cap, const StSlot *__restrict__ st, int64_t cutoff,
+                                                     uint64_t n_ips, uint32_t *__restrict__ keep,
+                                                     unsigned long long *__restrict__ cnt) {
+  uint64_t n = 0, z = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < st_cap; i += (uint64_t)gridDim.x * blockDim.x) {
+    const StSlot v = st[i];
+    if (st_survives(v, cutoff, n_ips)) {
+      keep[(v.key >> 24) - 1] = 1u;  // every writer stores the same value
+      ++n;
+    }
+  }
+  block_sum2(n, z);
+  if (threadIdx.x == 0 && n) atomicAdd(&cnt[0], (unsigned long long)n);
+}
+// klen[id] = the arena bytes IP id keeps, over [0, n_ips] (the last entry 0:
+// the scans' totals land there)
+__global__ void k_exp_len(uint64_t n_ips, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ ip_len,
+                          uint64_t *__restrict__ klen) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n_ips) return;
+  klen[i] = i < n_ips && keep[i] ? ip_len[i] : 0;
+}
+// kept IP id -> its bytes, offset and length under the new id
+__global__ void k_exp_arena(uint64_t n_ips, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ nid,
+                            const uint64_t *__restrict__ noff, const uint64_t *__restrict__ o_off,
+                            const uint32_t *__restrict__ o_len, const uint8_t *__restrict__ o_arena, uint64_t o_used,
+                            uint8_t *__restrict__ n_arena, uint64_t n_arena_cap, uint64_t *__restrict__ n_off,
+                            uint32_t *__restrict__ n_len) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_ips || !keep[i]) return;
+  const uint32_t len = o_len[i];
+  const uint64_t so = o_off[i], d = noff[i];
+  if (so + len > o_used || d + len > n_arena_cap) return;  // (not from a finished batch)
+  for (uint32_t k = 0; k < len; ++k) n_arena[d + k] = o_arena[so + k];
+  n_off[nid[i]] = d;
+  n_len[nid[i]] = len;
+}
+__global__ void k_exp_st(uint64_t old_cap, const StSlot *__restrict__ o, int64_t cutoff, uint64_t n_ips,
+                         const uint32_t *__restrict__ nid, StSlot *__restrict__ nt, uint64_t nmask) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= old_cap) return;
+  const StSlot v = o[i];
+  if (!st_survives(v, cutoff, n_ips)) return;
+  const uint64_t key = ((uint64_t)(nid[(v.key >> 24) - 1] + 1) << 24) | (v.key & 0xFFFFFFull);
+  uint64_t j = mix64(key) & nmask;
+  for (;;) {
+    const unsigned long long prev = atomicCAS((unsigned long long *)&nt[j].key, 0ull, (unsigned long long)key);
+    if (prev == 0) { nt[j].hits = v.hits; nt[j].start = v.start; nt[j].valid = v.valid; return; }
+    j = (j + 1) & nmask;
+  }
+}
+__global__ void k_exp_ip(uint64_t old_cap, const IpSlot *__restrict__ o, uint64_t n_ips, const uint32_t *__restrict__ keep,
+                         const uint32_t *__restrict__ nid, IpSlot *__restrict__ nt, uint64_t nmask) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= old_cap) return;
+  const IpSlot v = o[i];
+  if (v.hash == 0 || v.id >= n_ips || !keep[v.id]) return;
+  uint64_t j = v.hash & nmask;
+  for (;;) {
+    const unsigned long long prev = atomicCAS((unsigned long long *)&nt[j].hash, 0ull, (unsigned long long)v.hash);
+    if (prev == 0) { nt[j].id = nid[v.id]; nt[j].born = v.born; nt[j].key16 = v.key16; return; }
+    j = (j + 1) & nmask;
+  }
+}
+__global__ void k_exp_counters(uint64_t *__restrict__ counters, uint64_t ips, uint64_t bytes, uint64_t states) {
+  if (blockIdx.x || threadIdx.x) return;
+  counters[0] = ips;
+  counters[1] = bytes;
+  counters[2] = states;
+}
+
 // --------------------------------------------------------------- multi-GPU exchange
 // The partition runs over the lines in tiles of `steps` x kBlock lines (one
 // block each, one line per lane per step), in line order: k_part_count sums
@@ -4992,6 +5073,7 @@ struct bjx_engine {
   // persistent state
   State S{};
   uint64_t ip_cap = 0, st_cap = 0;
+  uint64_t ip_cap0 = 0, st_cap0 = 0, arena_cap0 = 0;  // as created: the floor bjx_state_expire shrinks to
   uint64_t rehashes = 0;
   uint64_t last_new_ips = 0, last_new_states = 0;  // entries the last batch created (capacity prediction)
   uint32_t epoch = 0;  // batch counter (IpSlot.born)
@@ -5073,6 +5155,7 @@ struct bjx_engine {
 
   // the batch between its match phase and its finish (bjx_match_batch / bjx_finish_batch)
   BatchCtx bc;
+  bool batch_open = false;  // bjx_match_batch done, its bjx_finish_batch* not yet (no bjx_state_expire in between)
   // multi-GPU exchange workspace
   DevBuf<uint32_t> pack_src, rx_len, rx_ev_el;
   DevBuf<uint64_t> pk_hist, pk_off, pk_counts, pk_bbase, rx_hash, rx_pos, rx_nev, rx_evoff;
@@ -6700,6 +6783,7 @@ extern "C" int bjx_engine_create(int device, const bjx_engine_options *opts, bjx
     uint64_t stc = std::max<uint64_t>(opts && opts->state_capacity ? next_pow2(opts->state_capacity) : 0, 1ull << 22);
     uint64_t ar = opts && opts->ip_arena_bytes ? opts->ip_arena_bytes : (64ull << 20);
     alloc_state(e.get(), ipc, stc, ar);
+    e->ip_cap0 = ipc; e->st_cap0 = stc; e->arena_cap0 = ar;
     *out = e.release();
     return BJX_OK;
   } catch (const BjxError &x) {
@@ -7942,6 +8026,7 @@ static void run_batch(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *bytes
   // a standalone batch has no exchange: no node batch's figure carries over
   e->exchange_ms = 0;
   e->xev_rec = false;
+  e->batch_open = false;
   e->counters_fresh = false;
   e->want_counters = true;
   struct Reset {  // whatever way match_phase leaves
@@ -7999,6 +8084,7 @@ extern "C" int bjx_match_batch(bjx_engine *e, const bjx_ruleset *rs, const uint8
     e->exchange_ms = 0;  // set by this batch's bjx_events_partition .. apply, if any
     e->xev_rec = false;
     match_phase(e, rs, bytes, n, now_ns, flags, out);
+    e->batch_open = true;
     return BJX_OK;
   });
 }
@@ -8158,6 +8244,7 @@ extern "C" int bjx_finish_batch(bjx_engine *e, const uint8_t *d_outcomes, uint32
   return guarded(e, [&]() -> int {
     const BatchCtx &c = e->bc;
     memset(out, 0, sizeof *out);
+    e->batch_open = false;
     if (!c.live) return BJX_OK;
     if (c.n_ev) {
       if (!e->partitioned || e->pk_n_ev != c.n_ev || !d_outcomes) throw BjxError(BJX_ERR_ARG, "bjx_finish_batch without a packed batch");
@@ -8226,6 +8313,7 @@ extern "C" int bjx_finish_batch_trips(bjx_engine *e, const uint32_t *d_trips, ui
   return guarded(e, [&]() -> int {
     const BatchCtx &c = e->bc;
     memset(out, 0, sizeof *out);
+    e->batch_open = false;
     if (!c.live) return BJX_OK;
     if (c.n_ev) {
       if (!e->partitioned || e->pk_n_ev != c.n_ev) throw BjxError(BJX_ERR_ARG, "bjx_finish_batch_trips without a packed batch");
@@ -8434,6 +8522,164 @@ extern "C" int bjx_state_clear(bjx_engine *e) {
   } catch (const BjxError &x) {
     e->last_error = x.what();
     return x.code;
+  }
+}
+
+namespace {
+uint64_t state_device_bytes(uint64_t ip_cap, uint64_t st_cap, uint64_t arena_cap) {
+  return ip_cap * (sizeof(IpSlot) + 4 + 8 + 4) + st_cap * sizeof(StSlot) + arena_cap;
+}
+// device allocations of one expiry: freed on every way out unless taken
+struct ExpAlloc {
+  std::vector<void *> ptrs;
+  bool nomem = false;
+  template <typename T>
+  T *get(uint64_t n) {
+    void *p = nullptr;
+    if (nomem) return nullptr;
+    if (hipMalloc(&p, std::max<uint64_t>(n, 1) * sizeof(T)) != hipSuccess) {
+      (void)hipGetLastError();  // the failed allocation is reported as BJX_ERR_NOMEM, not left pending
+      nomem = true;
+      return nullptr;
+    }
+    ptrs.push_back(p);
+    return static_cast<T *>(p);
+  }
+  void take() { ptrs.clear(); }
+  ~ExpAlloc() {
+    for (void *p : ptrs) (void)hipFree(p);
+  }
+};
+}  // namespace
+
+// Expiry: mark the IPs that keep a state, scan them into new dense ids (order
+// kept) and arena offsets, then build new tables from the survivors and swap.
+// The old tables are only read until the swap, so every failure before it
+// leaves the state as it was.
+extern "C" int bjx_state_expire(bjx_engine *e, int64_t cutoff_ns, bjx_expire_stats *out) {
+  if (!e) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  hipEvent_t ev[4] = {};
+  struct EvFree {
+    hipEvent_t *ev;
+    ~EvFree() {
+      for (int k = 0; k < 4; ++k)
+        if (ev[k]) (void)hipEventDestroy(ev[k]);
+    }
+  } ev_free{ev};
+  try {
+    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_expire between bjx_match_batch and its bjx_finish_batch");
+    HIP_OK(hipSetDevice(e->device));
+    HIP_OK(hipDeviceSynchronize());  // nothing of an earlier batch may land after the rebuild
+    State &S = e->S;
+    hipStream_t st = e->stream;
+    for (auto &x : ev) HIP_OK(hipEventCreate(&x));
+    read_counters(e);
+    e->counters_fresh = false;
+    const uint64_t n_ips = e->host_counters[0], used = e->host_counters[1], n_st = e->host_counters[2];
+    if (n_ips >= 0x7FFFFFFFull) throw BjxError(BJX_ERR_CAPACITY, "more than 2^31 distinct IPs");
+    const uint64_t bytes_before = state_device_bytes(e->ip_cap, e->st_cap, S.arena_cap);
+
+    // mark, lengths, scans (temporaries only)
+    ExpAlloc tmp;
+    uint32_t *keep = tmp.get<uint32_t>(n_ips + 1), *nid = tmp.get<uint32_t>(n_ips + 1);
+    uint64_t *klen = tmp.get<uint64_t>(n_ips + 1), *noff = tmp.get<uint64_t>(n_ips + 1);
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_expire: no device memory for the scan buffers");
+    e->chk.ensure(8);
+    HIP_OK(hipEventRecord(ev[0], st));
+    HIP_OK(hipMemsetAsync(keep, 0, (n_ips + 1) * 4, st));
+    HIP_OK(hipMemsetAsync(e->chk.p, 0, 8, st));
+    hipLaunchKernelGGL(k_exp_mark, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st, e->st_cap,
+                       S.st, cutoff_ns, n_ips, keep, e->chk.p);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_exp_len, dim3(grid_for(n_ips + 1)), dim3(kBlock), 0, st, n_ips, keep, S.ip_len, klen);
+    HIP_OK(hipGetLastError());
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, keep, nid, (int)(n_ips + 1), st); });
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, klen, noff, (int)(n_ips + 1), st); });
+    HIP_OK(hipEventRecord(ev[1], st));
+    unsigned long long kept_st = 0;
+    uint32_t kept_ips32 = 0;
+    uint64_t kept_bytes = 0;
+    pin_get(e, &kept_st, e->chk.p, 8);
+    pin_get(e, &kept_ips32, nid + n_ips, 4);
+    pin_get(e, &kept_bytes, noff + n_ips, 8);
+    pin_sync(e);
+    const uint64_t kept_ips = kept_ips32;
+    if (kept_ips > n_ips || kept_bytes > used || kept_st > e->st_cap)
+      throw BjxError(BJX_ERR_DEVICE, "internal: expiry counts exceed the tables");
+
+    // the new tables: growth's sizing rule on the survivors, never below the
+    // capacity the engine was created with and never above the present one
+    const uint64_t ip_cap = std::min(e->ip_cap, std::max(e->ip_cap0, next_pow2(kept_ips * 4 / 3 + 1024)));
+    const uint64_t st_cap = std::min(e->st_cap, std::max(e->st_cap0, next_pow2(kept_st * 4 / 3 + 1024)));
+    const uint64_t arena_cap = std::min(S.arena_cap, std::max(e->arena_cap0, next_pow2(2 * kept_bytes + 4096)));
+    ExpAlloc nw;
+    IpSlot *n_ip = nw.get<IpSlot>(ip_cap);
+    uint32_t *n_first = nw.get<uint32_t>(ip_cap);
+    uint64_t *n_off = nw.get<uint64_t>(ip_cap);
+    uint32_t *n_len = nw.get<uint32_t>(ip_cap);
+    uint32_t *n_ipst = nw.get<uint32_t>(ip_cap);
+    uint8_t *n_arena = nw.get<uint8_t>(arena_cap);
+    StSlot *n_stt = nw.get<StSlot>(st_cap);
+    if (nw.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_expire: no device memory for the new tables (state unchanged)");
+    HIP_OK(hipEventRecord(ev[2], st));
+    HIP_OK(hipMemsetAsync(n_ip, 0, ip_cap * sizeof(IpSlot), st));
+    HIP_OK(hipMemsetAsync(n_first, 0xFF, ip_cap * 4, st));
+    HIP_OK(hipMemsetAsync(n_ipst, 0xFF, ip_cap * 4, st));
+    HIP_OK(hipMemsetAsync(n_stt, 0, st_cap * sizeof(StSlot), st));
+    if (n_ips) {
+      hipLaunchKernelGGL(k_exp_arena, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, keep, nid, noff, S.ip_off, S.ip_len,
+                         S.arena, used, n_arena, arena_cap, n_off, n_len);
+      HIP_OK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_exp_st, dim3(grid_for(e->st_cap)), dim3(kBlock), 0, st, e->st_cap, S.st, cutoff_ns, n_ips, nid, n_stt,
+                       st_cap - 1);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_exp_ip, dim3(grid_for(e->ip_cap)), dim3(kBlock), 0, st, e->ip_cap, S.ip, n_ips, keep, nid, n_ip,
+                       ip_cap - 1);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(ev[3], st));
+    HIP_OK(hipStreamSynchronize(st));
+
+    // swap; what is keyed by slot index or IP id starts over (ip_first, the
+    // ip_st slot cache: new and all ~0; sort2_hold as bjx_state_clear)
+    nw.take();
+    for (void *p : {(void *)S.ip, (void *)S.ip_first, (void *)S.ip_off, (void *)S.ip_len, (void *)S.ip_st, (void *)S.arena,
+                    (void *)S.st})
+      (void)hipFree(p);
+    S.ip = n_ip; S.ip_first = n_first; S.ip_off = n_off; S.ip_len = n_len; S.ip_st = n_ipst; S.arena = n_arena; S.st = n_stt;
+    S.ip_mask = ip_cap - 1;
+    S.st_mask = st_cap - 1;
+    S.arena_cap = arena_cap;
+    S.ip_st_cap = ip_cap;
+    if (st_cap > (1ull << 32)) S.hot_name = kNone;
+    else if (e->st_cap > (1ull << 32)) e->bound_uid = 0;  // back under 2^32 slots: the next batch re-binds and may cache again
+    e->ip_cap = ip_cap;
+    e->st_cap = st_cap;
+    e->sort2_hold = 0;
+    hipLaunchKernelGGL(k_exp_counters, dim3(1), dim3(64), 0, st, S.counters, kept_ips, kept_bytes, (uint64_t)kept_st);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(st));
+    e->host_counters[0] = kept_ips; e->host_counters[1] = kept_bytes; e->host_counters[2] = kept_st;
+    e->counters_fresh = false;  // the next stage reads them again
+    if (out) {
+      float a = 0, b = 0;
+      HIP_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
+      HIP_OK(hipEventElapsedTime(&b, ev[2], ev[3]));
+      out->states_before = n_st; out->states_dropped = n_st - std::min<uint64_t>(n_st, kept_st);
+      out->ips_before = n_ips; out->ips_dropped = n_ips - kept_ips;
+      out->arena_bytes_before = used; out->arena_bytes_after = kept_bytes;
+      out->device_bytes_before = bytes_before;
+      out->device_bytes_after = state_device_bytes(ip_cap, st_cap, arena_cap);
+      out->device_ms = (double)a + (double)b;
+    }
+    return BJX_OK;
+  } catch (const BjxError &x) {
+    e->last_error = x.what();
+    return x.code;
+  } catch (const std::bad_alloc &) {
+    e->last_error = "host out of memory";
+    return BJX_ERR_NOMEM;
   }
 }
 

@@ -270,7 +270,9 @@ struct Lines {
 constexpr uint32_t kCandFirstLits = 8;
 
 // Persistent rate-limit state (RegexRateLimitStates, rate_limit.go:17-21),
-// keyed by IP string and rule name, never evicted (as in the reference).
+// keyed by IP string and rule name; never evicted by a batch (as in the
+// reference), only by the host's explicit bjx_state_expire, which rebuilds the
+// tables from the survivors with the IP ids renumbered densely in order.
 //   IP table: open addressing on the 64-bit hash of the IP bytes, one 16 B
 //   slot per probe; the IP bytes live in the arena (id -> offset, length) and
 //   every lookup of an IP created in an earlier batch compares them in full.

@@ -815,6 +815,27 @@ extern "C" int bjx_node_state_stats_get(bjx_node *n, bjx_state_stats *out) {
   return BJX_OK;
 }
 
+// every shard with the same cutoff (the node lock keeps it out of a node
+// batch's phases); a shard that fails leaves the earlier ones expired, which
+// is a legal state: each shard's expiry stands on its own
+extern "C" int bjx_node_state_expire(bjx_node *n, int64_t cutoff_ns, bjx_expire_stats *out) {
+  if (!n) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(n->mu);
+  bjx_expire_stats t{};
+  for (auto &P : n->parts) {
+    bjx_expire_stats s{};
+    const int rc = bjx_state_expire(P.e, cutoff_ns, &s);
+    if (rc != BJX_OK) return rc;
+    t.states_before += s.states_before; t.states_dropped += s.states_dropped;
+    t.ips_before += s.ips_before; t.ips_dropped += s.ips_dropped;
+    t.arena_bytes_before += s.arena_bytes_before; t.arena_bytes_after += s.arena_bytes_after;
+    t.device_bytes_before += s.device_bytes_before; t.device_bytes_after += s.device_bytes_after;
+    if (s.device_ms > t.device_ms) t.device_ms = s.device_ms;
+  }
+  if (out) *out = t;
+  return BJX_OK;
+}
+
 extern "C" int bjx_node_state_clear(bjx_node *n) {
   if (!n) return BJX_ERR_ARG;
   std::lock_guard<std::mutex> g(n->mu);

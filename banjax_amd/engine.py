@@ -312,6 +312,14 @@ class Engine:
     def state_clear(self):
         self._check(_lib.lib().bjx_state_clear(self._h), "state_clear")
 
+    def state_expire(self, cutoff_ns: int) -> dict:
+        """Drop every state whose window started before cutoff_ns and every IP
+        left without one; the tables are rebuilt and shrink (bjx_state_expire).
+        Returns the bjx_expire_stats fields."""
+        st = _lib.ExpireStats()
+        self._check(_lib.lib().bjx_state_expire(self._h, cutoff_ns, C.byref(st)), "state_expire")
+        return {k: getattr(st, k) for k, _ in _lib.ExpireStats._fields_}
+
     def state_dump(self) -> str:
         n = _lib.lib().bjx_state_dump(self._h, None, 0)
         buf = C.create_string_buffer(n + 1)
@@ -428,6 +436,12 @@ class Node:
 
     def state_clear(self):
         self._check(_lib.lib().bjx_node_state_clear(self._h), "node_state_clear")
+
+    def state_expire(self, cutoff_ns: int) -> dict:
+        """Engine.state_expire on every shard: stats summed, device_ms the slowest shard's."""
+        st = _lib.ExpireStats()
+        self._check(_lib.lib().bjx_node_state_expire(self._h, cutoff_ns, C.byref(st)), "node_state_expire")
+        return {k: getattr(st, k) for k, _ in _lib.ExpireStats._fields_}
 
     def state_dump(self) -> str:
         n = _lib.lib().bjx_node_state_dump(self._h, None, 0)

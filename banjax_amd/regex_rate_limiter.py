@@ -401,6 +401,26 @@ class MockBanner(Banner):
 
 # ------------------------------------------------------------ the tailer
 
+OLD_LINE_NS = 10 * 1_000_000_000  # consumeLine drops lines older than now - 10 s (regex_rate_limiter.go:164-167)
+_INT64_MIN, _INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def expire_cutoff_ns(now_ns: int, cfg: Config) -> int:
+    """The trip-transparent cutoff of Engine.state_expire (include/banjax_gpu.h):
+
+        now_ns - 10 s - max(interval over the global and per-site rules)
+
+    A state whose window started before it can only meet OutsideInterval
+    events from now on (no later line is older than now - 10 s, and
+    t - start > Interval then holds for every rule that can own the state), so
+    dropping it changes no trip.  An interval <= 0 counts as 0 (every later
+    event of such a rule is outside its window anyway); with no rules the
+    maximum is 0.  Saturating: a result below INT64_MIN is INT64_MIN, which
+    expires nothing."""
+    longest = max([r.interval for r in cfg.all_rules()] + [0])
+    return max(_INT64_MIN, min(_INT64_MAX, int(now_ns) - OLD_LINE_NS - longest))
+
+
 class RegexRateLimitStates:
     """RegexRateLimitStates (rate_limit.go:17-103) backed by the engine's HBM tables."""
 
@@ -499,6 +519,15 @@ class RegexRateLimiter:
             snap = self._snap
             out = self.engine.process(snap.ruleset, data, now_ns, copy_results=want_results, **self._ban_kw())
             return self._finish(snap, data, out, now_ns, want_results)
+
+    def expire_states(self, now_ns: int) -> dict:
+        """Drop the rate-limit state no later line can hit inside its window
+        (expire_cutoff_ns of the current config) and shrink the tables; changes
+        no trip.  Never called implicitly: the host decides when (the
+        reference's 29 s metrics ticker is the natural place).  now_ns must not
+        run behind the clock the batches were given.  Returns the expiry stats."""
+        with self._mu:
+            return self.engine.state_expire(expire_cutoff_ns(now_ns, self._snap.config))
 
     def _ban_kw(self):
         if not self.device_bans:

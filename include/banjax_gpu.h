@@ -102,7 +102,8 @@ int bjx_ruleset_rule_info(const bjx_ruleset *rs, size_t rule_idx, uint32_t *dfa_
                           uint32_t *flags);
 
 typedef struct bjx_engine_options {
-  uint64_t ip_capacity;       /* distinct IPs kept (reference never evicts, rate_limit.go:45-67); 0 = default */
+  uint64_t ip_capacity;       /* distinct IPs kept (the reference never evicts, rate_limit.go:45-67; here eviction is
+                                 explicit and opt-in, bjx_state_expire, which also shrinks back to this); 0 = default */
   uint64_t state_capacity;    /* distinct (ip, rule name) states; 0 = default */
   uint64_t ip_arena_bytes;    /* bytes of IP strings; 0 = default */
 } bjx_engine_options;
@@ -244,10 +245,11 @@ int bjx_state_get(bjx_engine *e, const char *ip, size_t ip_len, const char *name
 /* RegexRateLimitStates.Len(): number of distinct IPs with state. */
 int64_t bjx_state_len(bjx_engine *e);
 /* Occupancy of the persistent rate-limit state in HBM.  The reference never
-   evicts state (rate_limit.go:45-67) and neither does the engine: the tables
-   grow (rehashed on the device, 3/4 load factor) until a batch's growth
-   cannot be allocated, which returns BJX_ERR_CAPACITY; device_bytes lets the
-   host watch that coming (metrics, alongside Len(): config.go:165). */
+   evicts state (rate_limit.go:45-67) and the engine never does on its own:
+   the tables grow (rehashed on the device, 3/4 load factor) until a batch's
+   growth cannot be allocated, which returns BJX_ERR_CAPACITY; device_bytes
+   lets the host watch that coming (metrics, alongside Len(): config.go:165).
+   Eviction is explicit and opt-in: bjx_state_expire below. */
 typedef struct bjx_state_stats {
   uint64_t ips;            /* distinct IP strings (RegexRateLimitStates.Len) */
   uint64_t ip_slots;       /* IP table capacity */
@@ -261,6 +263,47 @@ typedef struct bjx_state_stats {
 int bjx_state_stats_get(bjx_engine *e, bjx_state_stats *out);
 /* Drop every rate-limit state (a fresh RegexRateLimitStates). */
 int bjx_state_clear(bjx_engine *e);
+
+/* ---- Explicit expiry of stale state (no counterpart in the reference, which
+   is restarted often enough to get away without one).
+   Drops every state whose interval_start_ns < cutoff_ns and every IP left
+   with no state, and compacts what survives into new tables sized by the
+   growth rule (3/4 load factor) on the survivor counts, never below the
+   capacities the engine was created with: the tables shrink.  Surviving IPs
+   keep their relative (first-seen) order in bjx_state_dump; rehashes does not
+   count an expiry.  Nothing calls it implicitly.
+
+   Contract.  Apply (rate_limit.go:37-78) writes {1, t} both for a state it
+   does not know (FirstTime) and for one whose window is over (t - start >
+   Interval: OutsideInterval), then runs the same NumHits > HitsPerInterval
+   check.  So forgetting a state whose next event would be OutsideInterval
+   changes no Exceeded, no stored state and no later event of that key; the
+   one RuleResult of that next event reads match_type FIRST_TIME instead of
+   OUTSIDE_INTERVAL, and the first RuleResult of an IP all of whose states
+   went (whichever rule it is for) reads seen_ip 0 instead of 1.
+   Len / Get / String stop listing what was dropped.  Lines older than
+   now - 10 s never reach Apply (OldLine, regex_rate_limiter.go:164-167), so
+   while the host's now_ns never goes backwards and no reload lengthens an
+   interval,
+       cutoff = now_ns - 10 s - max(interval_ns over all rules of the config)
+   (saturating int64; on underflow INT64_MIN: nothing is dropped) drops only
+   such states: the expiry is trip-transparent.  Any other cutoff is allowed
+   and simply means "those states are forgotten"; INT64_MAX equals
+   bjx_state_clear in everything a caller can observe.
+
+   Takes the engine lock like the other bjx_state_* calls.  Not legal between
+   bjx_match_batch and the bjx_finish_batch* that closes it (BJX_ERR_ARG; the
+   node call waits for the node batch instead).  The new tables are allocated
+   before the old ones are freed: BJX_ERR_NOMEM leaves the state untouched and
+   usable.  out may be NULL. */
+typedef struct bjx_expire_stats {
+  uint64_t states_before, states_dropped;
+  uint64_t ips_before, ips_dropped;
+  uint64_t arena_bytes_before, arena_bytes_after;
+  uint64_t device_bytes_before, device_bytes_after;  /* as bjx_state_stats.device_bytes */
+  double device_ms;                                  /* device time of the pass (HIP events) */
+} bjx_expire_stats;
+int bjx_state_expire(bjx_engine *e, int64_t cutoff_ns, bjx_expire_stats *out);
 /* RegexRateLimitStates.String(): "ip:\n\trule:\n\t\t{hits start}\n" blocks, IPs in
    first-seen order.  Returns the full length (writes at most cap bytes). */
 size_t bjx_state_dump(bjx_engine *e, char *out, size_t cap);
@@ -414,6 +457,9 @@ int64_t bjx_node_state_len(bjx_node *n);
 size_t bjx_node_state_dump(bjx_node *n, char *out, size_t cap);
 int bjx_node_state_stats_get(bjx_node *n, bjx_state_stats *out);
 int bjx_node_state_clear(bjx_node *n);
+/* bjx_state_expire on every shard with the same cutoff: counts and bytes
+   summed, device_ms the slowest shard's.  out may be NULL. */
+int bjx_node_state_expire(bjx_node *n, int64_t cutoff_ns, bjx_expire_stats *out);
 
 int bjx_abi_version(void);
 
