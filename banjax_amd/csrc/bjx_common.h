@@ -164,6 +164,51 @@ BJX_HD int64_t go_sub(int64_t t, int64_t u) {
   return d;
 }
 
+// ------------------------------------------------------------- fixed windows
+//
+// RegexRateLimitStates.Apply (reference internal/rate_limit.go:37-78) over the
+// events of one state, in closed form.  A window opens at its first event's
+// timestamp t0 and holds every following event until the first one (in event
+// order, whatever the timestamps' order) that lies more than the interval
+// past t0; that event opens the next window.  The hot-key kernels (k_long_*)
+// and the wave-per-run path of k_bucket_apply share the two rules below;
+// tests/cpu/wave_runs.cpp checks them against the event-by-event walk.
+
+// the event at ts does not belong to the window opened at t0
+BJX_HD bool window_past(int64_t ts, int64_t t0, int64_t interval) { return go_sub(ts, t0) > interval; }
+
+// One event of Apply as the reference writes it, on the state (valid, hits,
+// start): its MatchType to mt (0 FirstTime, 1 OutsideInterval, 2
+// InsideInterval: bjx_match_type), returns Exceeded.
+BJX_HD bool window_step(int64_t ts, int64_t interval, int64_t limit, bool &valid, int64_t &hits, int64_t &start, uint32_t &mt) {
+  if (!valid) { hits = 1; start = ts; mt = 0; valid = true; }
+  else if (window_past(ts, start, interval)) { mt = 1; hits = 1; start = ts; }
+  else { mt = 2; ++hits; }
+  const bool ex = hits > limit;
+  if (ex) hits = 0;
+  return ex;
+}
+
+// a % b for a >= 0, b > 0 (32-bit division when both fit: the device has no
+// 64-bit divider)
+BJX_HD int64_t mod_pos(int64_t a, int64_t b) {
+  if ((((uint64_t)a | (uint64_t)b) >> 32) == 0) return (int64_t)((uint32_t)a % (uint32_t)b);
+  return a % b;
+}
+
+// NumHits after the e-th event (e >= 1) counted into a window that held h0
+// hits before the first of them (h0 = 0 for a window opened by that event:
+// Apply sets NumHits = 1 there).  That event is Exceeded iff the result is 0:
+// a hit that brings NumHits past the limit resets it to 0, so hits trip every
+// limit + 1 events; with h0 > limit (a reload lowered the limit) the first
+// event trips at once, with limit < 0 every event does.
+BJX_HD int64_t window_hits(int64_t h0, int64_t e, int64_t limit) {
+  if (limit < 0) return 0;
+  if (limit == INT64_MAX) return h0 + e;  // never past the limit
+  if (h0 > limit) return mod_pos(e - 1, limit + 1);
+  return mod_pos(h0 + e, limit + 1);
+}
+
 // int64(f * 1e9) with amd64 CVTTSD2SQ semantics (out of range/NaN -> MinInt64).
 BJX_HD int64_t ns_from_seconds(double f) {
   double x = f * 1e9;

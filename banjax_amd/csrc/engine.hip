@@ -3505,20 +3505,24 @@ __global__ void k_fold_claims(State S) {
 // sorted order: bit0 seenIp, bits1-2 MatchType, bit3 Exceeded, bit7 valid.
 constexpr uint32_t kApplyChunk = 2048;
 
+// an outcome byte of out_sorted
+__device__ __forceinline__ uint8_t outcome_byte(bool seen, uint32_t mt, bool ex) {
+  return (uint8_t)(0x80 | (seen ? 1 : 0) | (mt << 1) | (ex ? 8 : 0));
+}
+
+__device__ __forceinline__ uint8_t apply_event(uint32_t r, bool seen, int64_t ts, const DevRule *__restrict__ rules, uint32_t &pr,
+                                               int64_t &interval, int64_t &limit, bool &valid, int64_t &hits, int64_t &start) {
+  if (r != pr) { pr = r; interval = rules[r].interval_ns; limit = rules[r].hits; }  // rules sharing a name share the state
+  static_assert(BJX_FIRST_TIME == 0 && BJX_OUTSIDE_INTERVAL == 1 && BJX_INSIDE_INTERVAL == 2, "window_step's MatchType");
+  uint32_t mt;
+  const bool ex = window_step(ts, interval, limit, valid, hits, start, mt);
+  return outcome_byte(seen, mt, ex);
+}
+
 template <typename R>
 __device__ __forceinline__ uint8_t apply_step(const R &v, int64_t base, const DevRule *__restrict__ rules, uint32_t &pr,
                                               int64_t &interval, int64_t &limit, bool &valid, int64_t &hits, int64_t &start) {
-  const uint32_t r = v.rule_id();
-  const bool seen = v.seen();
-  const int64_t ts = v.time(base);
-  if (r != pr) { pr = r; interval = rules[r].interval_ns; limit = rules[r].hits; }  // rules sharing a name share the state
-  uint8_t mt;
-  if (!valid) { hits = 1; start = ts; mt = BJX_FIRST_TIME; valid = true; }
-  else if (go_sub(ts, start) > interval) { mt = BJX_OUTSIDE_INTERVAL; hits = 1; start = ts; }
-  else { mt = BJX_INSIDE_INTERVAL; ++hits; }
-  const bool ex = hits > limit;
-  if (ex) hits = 0;
-  return (uint8_t)(0x80 | (seen ? 1 : 0) | (mt << 1) | (ex ? 8 : 0));
+  return apply_event(v.rule_id(), v.seen(), v.time(base), rules, pr, interval, limit, valid, hits, start);
 }
 
 template <typename R>
@@ -3625,24 +3629,196 @@ __global__ __launch_bounds__(kBlock) void k_apply(uint64_t n_ev, const uint32_t 
 constexpr int kBucketBits = 16;
 constexpr uint32_t kBucketItems = 16;
 constexpr uint32_t kBucketCap = kBlock * kBucketItems;  // 4096 events
+constexpr uint32_t kWaveRun = 8;  // runs at least this long go to a whole wave (bucket_wave_runs)
 
-// bstart[b] = first sorted position whose bucket (key >> L) is >= b, b <= nb
+// bstart[b] = first sorted position whose bucket (key >> L) is >= b, b <= nb.
+// Four positions per lane, their keys in one 16-byte load (key is 16-byte
+// aligned); the key before a lane's four comes from the lane below, from
+// memory for a wave's first lane only.  (One position per lane, each key read
+// twice with 4-byte loads: 0.40 against 0.17 ms per cfg3 batch.)
 __global__ __launch_bounds__(kBlock) void k_bucket_bounds(uint64_t n_ev, const uint32_t *__restrict__ key, uint32_t L,
                                                           uint32_t nb, uint32_t *__restrict__ bstart) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > n_ev) return;
-  const uint32_t b = i < n_ev ? key[i] >> L : nb;
-  const uint32_t lo = i ? (key[i - 1] >> L) + 1 : 0u;
-  for (uint32_t x = lo; x <= b; ++x) bstart[x] = (uint32_t)i;
+  const uint64_t i0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  uint32_t k[4] = {0, 0, 0, 0};
+  if (i0 + 4 <= n_ev) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(key + i0);
+    k[0] = v.x; k[1] = v.y; k[2] = v.z; k[3] = v.w;
+  } else {
+    for (uint32_t j = 0; j < 4; ++j)
+      if (i0 + j < n_ev) k[j] = key[i0 + j];
+  }
+  uint32_t prev = __shfl_up(k[3], 1);
+  if ((threadIdx.x & 63) == 0 && i0 && i0 <= n_ev) prev = key[i0 - 1];
+#pragma unroll
+  for (uint32_t j = 0; j < 4; ++j) {
+    const uint64_t i = i0 + j;
+    if (i > n_ev) return;
+    const uint32_t b = i < n_ev ? k[j] >> L : nb;
+    const uint32_t lo = i ? (prev >> L) + 1 : 0u;
+    for (uint32_t x = lo; x <= b; ++x) bstart[x] = (uint32_t)i;
+    prev = k[j];
+  }
 }
+
+// The runs of k_bucket_apply that go to whole waves, in chunks of 64 events,
+// one lane per event: the chunk's rank -> position entries, records and (for a
+// rule other than the head's) rule limits are loaded by all lanes at once, so a
+// chunk waits for one memory latency where the lane-per-run walk waits for 64.
+// When every event of the chunk has the head rule's interval and limit, its
+// windows are found one after another (the first lane past the window's first
+// whose timestamp is window_past, by ballot: the first in event order, as the
+// event-by-event walk finds it, so the timestamps need not be ordered) and
+// each lane's outcome follows from its place in its window (window_hits), as
+// in k_long_fill.  Otherwise every lane steps through the chunk's events with
+// apply_event (each event broadcast) and lane i keeps event i's outcome.
+// Either way the chunk starts from (valid, hits, start) and leaves them for the
+// next one: the slot before the first chunk, written back after the last.
+
+// one chunk: na events, this lane's at position p with record rv (lanes >= na
+// hold the chunk's first event again and store nothing); first: the run's
+// first chunk, which sets the head rule r0 and its interval I and limit Lim
+template <typename R>
+__device__ __forceinline__ void wave_chunk(uint32_t u0, uint32_t p, const R &rv, uint32_t na, bool first, int64_t tbase,
+                                           const DevRule *__restrict__ rules, uint32_t &r0, int64_t &I, int64_t &Lim,
+                                           bool &valid, int64_t &hits, int64_t &start, uint8_t *s_out,
+                                           uint32_t *__restrict__ wcnt) {
+  const uint32_t lane = threadIdx.x & 63;
+  const bool act = lane < na;
+  const uint32_t r = rv.rule_id();
+  const int64_t ts = rv.time(tbase);
+  if (first) {
+    r0 = __shfl(r, 0);
+    I = rules[r0].interval_ns;
+    Lim = rules[r0].hits;
+  }
+  bool same = true;
+  if (r != r0) same = rules[r].interval_ns == I && rules[r].hits == Lim;
+  uint32_t mt = BJX_INSIDE_INTERVAL;
+  bool ex = false;
+  if (__ballot(!same) == 0) {
+    // the current window: opened at Tw by lane a (-1: the stored window, which the chunk's
+    // first events go on counting into); per lane, its window's first lane in this chunk,
+    // the hits the window held before that lane, and that lane's MatchType
+    int32_t a = valid ? -1 : 0;
+    int64_t Tw = valid ? start : __shfl(ts, 0);
+    uint32_t wa = 0, wmt = valid ? BJX_INSIDE_INTERVAL : BJX_FIRST_TIME;
+    int64_t wh0 = valid ? hits : 0;
+    for (;;) {
+      const unsigned long long m = __ballot(act && (int32_t)lane > a && window_past(ts, Tw, I));
+      if (!m) break;
+      a = __ffsll(m) - 1;
+      Tw = __shfl(ts, a);
+      if ((int32_t)lane >= a) { wa = (uint32_t)a; wh0 = 0; wmt = BJX_OUTSIDE_INTERVAL; }
+    }
+    const int64_t hh = window_hits(wh0, (int64_t)(lane - wa) + 1, Lim);
+    ex = hh == 0;
+    if (lane == wa) mt = wmt;
+    hits = __shfl(hh, (int)na - 1);
+    start = Tw;
+    valid = true;
+  } else {
+    uint32_t pr = 0xFFFFFFFFu;
+    int64_t iv = 0, lm = 0;
+    for (uint32_t i = 0; i < na; ++i) {
+      const uint8_t o = apply_event(__shfl(r, (int)i), true, __shfl(ts, (int)i), rules, pr, iv, lm, valid, hits, start);
+      if (lane == i) { mt = (o >> 1) & 3u; ex = (o & 8) != 0; }
+    }
+  }
+  if (act) {
+    s_out[p] = outcome_byte(rv.seen(), mt, ex);
+    if (wcnt) atomicAdd(&wcnt[u0 + p], 1u);  // BJX_CHECK: writes per sorted position
+  }
+}
+
+// this wave's runs (runs wave, wave + 4, ... of the nwv listed down from s_ord_top), chunk
+// after chunk; the next chunk -- the run's next, or the first of the wave's next run with
+// that run's slot -- is loaded while the current one is applied
+template <typename R>
+__device__ __forceinline__ void bucket_wave_runs(const R *__restrict__ rec, uint32_t u0, uint32_t n, uint32_t nh, uint32_t nwv,
+                                                 const uint16_t *s_ord_top, const uint16_t *s_head, const uint16_t *s_lk,
+                                                 const uint16_t *s_perm, uint8_t *s_out, uint32_t qb, int64_t tbase,
+                                                 const DevRule *__restrict__ rules, StSlot *__restrict__ st,
+                                                 uint32_t *__restrict__ wcnt) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t t = threadIdx.x >> 6;
+  if (t >= nwv) return;
+  uint32_t b, e, q;
+  auto run_at = [&](uint32_t tt, uint32_t &bb, uint32_t &ee, uint32_t &qq) {
+    const uint32_t h = *(s_ord_top - tt);
+    bb = s_head[h];
+    ee = h + 1 < nh ? s_head[h + 1] : n;
+    qq = qb | s_lk[bb];
+  };
+  auto pos_at = [&](uint32_t cc, uint32_t ee) { return (uint32_t)s_perm[cc + (lane < ee - cc ? lane : 0u)]; };
+  run_at(t, b, e, q);
+  uint32_t c = b;
+  StSlot nslot = st[q];
+  uint32_t np = pos_at(c, e);
+  R nrv = rec[u0 + np];
+  bool valid = false;
+  int64_t hits = 0, start = 0, I = 0, Lim = 0;
+  uint32_t r0 = 0;
+  for (;;) {
+    const uint32_t p = np, na = min(64u, e - c);
+    const R rv = nrv;
+    const bool first = c == b, last = c + 64 >= e;
+    if (first) { valid = nslot.valid != 0; hits = nslot.hits; start = nslot.start; }
+    uint32_t t2 = t, b2 = b, e2 = e, q2 = q, c2 = c + 64;
+    if (last) {
+      t2 = t + kBlock / 64;
+      if (t2 < nwv) { run_at(t2, b2, e2, q2); c2 = b2; }
+    }
+    const bool more = t2 < nwv;
+    if (more) {
+      if (last) nslot = st[q2];
+      np = pos_at(c2, e2);
+      nrv = rec[u0 + np];
+    }
+    wave_chunk(u0, p, rv, na, first, tbase, rules, r0, I, Lim, valid, hits, start, s_out, wcnt);
+    if (last && lane == 0) {
+      st[q].hits = hits;
+      st[q].start = start;
+      st[q].valid = 1;
+    }
+    if (!more) break;
+    t = t2; b = b2; e = e2; q = q2; c = c2;
+  }
+}
+
+// Timing variants of k_bucket_apply (never the shipped build):
+// with -DBJX_BK_STOP=k the kernel stops after its stage k -- 1 the key load and
+// block sort, 2 head compaction and ordering, 3 the runs of at least kLongRun
+// events (the lanes' short runs are skipped) -- and stores "inside the
+// interval, not exceeded" for every event it did not reach, so the kernels
+// after it see ordinary outcomes.  -DBJX_BK_CENSUS counts, per batch, events
+// and runs in all, and in runs of >= 8, >= 16 and >= 64 events (stderr).
+#ifdef BJX_BK_STOP
+#define BJX_BK_STAGE(k)                                                           \
+  if (BJX_BK_STOP == (k)) {                                                       \
+    for (uint32_t i = tid; i < n; i += kBlock) out_sorted[u0 + i] = s_out[i];     \
+    return;                                                                       \
+  }
+#define BJX_BK_LANE_RUNS (BJX_BK_STOP == 3 ? nfront : nh - nwv)
+#else
+#define BJX_BK_STAGE(k)
+#define BJX_BK_LANE_RUNS (nh - nwv)
+#endif
+#ifdef BJX_BK_CENSUS
+__device__ unsigned long long g_bk_census[8];
+#endif
 
 // One bucket per block.  The low key bits are ranked by a stable block radix
 // sort of the bucket's (low bits << 12 | position) words on bits [12, 12 + L):
 // the position rides in the key's low bits, so the sort moves one word per
 // item and no value array; padding ranks take the largest low key and come
 // last (they sit after every real record in the sort's input order, which it
-// keeps for equal keys).  Run heads are compacted
-// in rank order and taken longest first, as in k_apply; a lane walks its run
+// keeps for equal keys).  Run heads are compacted in rank order.  Runs of at
+// least wave_min events (kWaveRun; ~0 with BJX_WAVE_RUNS=0) are dealt round
+// robin to the block's four waves, a whole wave per run (bucket_wave_runs): at
+// cfg3 the rule that matches every line gives each bucket ~29 runs of ~65
+// events, which one lane each would walk as ~65 dependent loads while most of
+// the block idles.  The other runs are taken longest first by one lane each,
+// as in k_apply; a lane walks its run
 // through the rank -> position table, loading each record from the bucket's
 // few KB of HBM / L2, the next one in flight while the current one is applied.
 // (Gathering the records into LDS in rank order first, 16 independent loads
@@ -3653,7 +3829,8 @@ __global__ __launch_bounds__(kBlock) void k_bucket_apply(const uint32_t *__restr
                                                          const uint32_t *__restrict__ bstart, uint32_t L, int64_t tbase,
                                                          const DevRule *__restrict__ rules, StSlot *__restrict__ st,
                                                          uint8_t *__restrict__ out_sorted, uint32_t *__restrict__ big,
-                                                         unsigned long long *__restrict__ n_big, uint32_t *__restrict__ wcnt) {
+                                                         unsigned long long *__restrict__ n_big, uint32_t *__restrict__ wcnt,
+                                                         uint32_t wave_min) {
   using Sort = hipcub::BlockRadixSort<uint32_t, kBlock, kBucketItems>;
   static_assert(kBucketCap <= 4096, "positions ride in 12 key bits");
   constexpr uint32_t kLongRun = 8;
@@ -3667,7 +3844,7 @@ __global__ __launch_bounds__(kBlock) void k_bucket_apply(const uint32_t *__restr
   uint16_t *const s_head = s_u.ho;
   uint16_t *const s_ord = s_u.ho + kBucketCap;  // run indices, long runs first
   __shared__ uint8_t s_out[kBucketCap];                     // by position
-  __shared__ uint32_t s_wsum[kBlock / 64], s_front, s_back;
+  __shared__ uint32_t s_wsum[kBlock / 64], s_front, s_back, s_nwave;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t bk = blockIdx.x, u0 = bstart[bk], n = bstart[bk + 1] - u0;
   if (n == 0) return;
@@ -3677,7 +3854,10 @@ __global__ __launch_bounds__(kBlock) void k_bucket_apply(const uint32_t *__restr
   }
   const uint32_t mask = (1u << L) - 1u;
   for (uint32_t i = tid; i < n; i += kBlock) s_u.lk[i] = key[u0 + i] & mask;
-  if (tid == 0) { s_front = 0; s_back = 0; }
+#ifdef BJX_BK_STOP
+  for (uint32_t i = tid; i < n; i += kBlock) s_out[i] = outcome_byte(true, BJX_INSIDE_INTERVAL, false);
+#endif
+  if (tid == 0) { s_front = 0; s_back = 0; s_nwave = 0; }
   __syncthreads();
   uint32_t k[kBucketItems];
 #pragma unroll
@@ -3695,6 +3875,7 @@ __global__ __launch_bounds__(kBlock) void k_bucket_apply(const uint32_t *__restr
     s_perm[r] = (uint16_t)(k[j] & 0xFFFu);
   }
   __syncthreads();
+  BJX_BK_STAGE(1)
   // run heads, compacted in rank order (block scan of per-thread counts)
   uint32_t fl = 0;
 #pragma unroll
@@ -3719,15 +3900,30 @@ __global__ __launch_bounds__(kBlock) void k_bucket_apply(const uint32_t *__restr
   for (uint32_t j = 0; fl; ++j, fl >>= 1)
     if (fl & 1) s_head[base++] = (uint16_t)(tid * kBucketItems + j);
   __syncthreads();
+  // s_ord: the lanes' long runs from the front, their short runs down from nh - 1, the waves'
+  // runs down from the top (wave_min >= 2, so nh plus the number of those runs is at most n)
   for (uint32_t h = tid; h < nh; h += kBlock) {
     const uint32_t len = (h + 1 < nh ? s_head[h + 1] : n) - s_head[h];
-    if (len >= kLongRun) s_ord[atomicAdd(&s_front, 1u)] = (uint16_t)h;
+    if (len >= wave_min) s_ord[kBucketCap - 1 - atomicAdd(&s_nwave, 1u)] = (uint16_t)h;
+    else if (len >= kLongRun) s_ord[atomicAdd(&s_front, 1u)] = (uint16_t)h;
     else s_ord[nh - 1 - atomicAdd(&s_back, 1u)] = (uint16_t)h;
+#ifdef BJX_BK_CENSUS
+    atomicAdd(&g_bk_census[0], (unsigned long long)len);
+    atomicAdd(&g_bk_census[1], 1ull);
+    for (uint32_t c = 0; c < 3; ++c)
+      if (len >= (8u << c * (c + 1) / 2)) {  // 8, 16, 64
+        atomicAdd(&g_bk_census[2 + 2 * c], (unsigned long long)len);
+        atomicAdd(&g_bk_census[3 + 2 * c], 1ull);
+      }
+#endif
   }
   __syncthreads();
+  BJX_BK_STAGE(2)
   const uint32_t qb = bk << L;
-  for (uint32_t t = tid; t < nh; t += kBlock) {
-    const uint32_t h = s_ord[t];
+  const uint32_t nwv = s_nwave, nfront = s_front;
+  bucket_wave_runs(rec, u0, n, nh, nwv, s_ord + kBucketCap - 1, s_head, s_lk, s_perm, s_out, qb, tbase, rules, st, wcnt);
+  for (uint32_t t = tid; t < BJX_BK_LANE_RUNS; t += kBlock) {
+    const uint32_t h = s_ord[t < nfront ? t : t + nwv];
     const uint32_t b = s_head[h], e = h + 1 < nh ? s_head[h + 1] : n;
     const uint32_t q = qb | s_lk[b];
     const StSlot cur = st[q];
@@ -3861,7 +4057,7 @@ __global__ __launch_bounds__(kBlock) void k_long_ends(uint64_t n_ev, const uint3
   const int64_t I = rules[rec[head].rule_id()].interval_ns;
   const int64_t ts = rec[head].time(base);
   const bool valid = cur.valid != 0;
-  const bool cont = valid && go_sub(ts, cur.start) <= I;
+  const bool cont = valid && !window_past(ts, cur.start, I);
   R.t0[r] = cont ? cur.start : ts;
   R.h0[r] = cont ? cur.hits : 0;
   R.flags[r] = (cont ? 1u : 0u) | ((uint32_t)(valid ? BJX_OUTSIDE_INTERVAL : BJX_FIRST_TIME) << 1) |
@@ -3933,15 +4129,10 @@ __global__ __launch_bounds__(kBlock) void k_long_windows(const uint32_t *__restr
     if (tid == 0) win[nw] = a;
     ++nw;
     const int64_t Tw = T;
-    const uint64_t b = block_first(a + 1, end, [&](uint64_t i) { return go_sub(rec[i].time(base), Tw) > I; }, s_red);
+    const uint64_t b = block_first(a + 1, end, [&](uint64_t i) { return window_past(rec[i].time(base), Tw, I); }, s_red);
     if (b >= end) {
       if (tid == 0) {
-        const int64_t e = (int64_t)(b - a);
-        int64_t hits;
-        if (Lim < 0) hits = 0;
-        else if (h0 > Lim) hits = (e - 1) % (Lim + 1);
-        else hits = (h0 + e) % (Lim + 1);
-        st[q].hits = hits;
+        st[q].hits = window_hits(h0, (int64_t)(b - a), Lim);
         st[q].start = Tw;
         st[q].valid = 1;
         R.nwin[r] = nw;
@@ -3977,15 +4168,11 @@ __global__ __launch_bounds__(kBlock) void k_long_fill(uint64_t total, const Rec 
   const bool first_win = lo == 0, cont = first_win && (fl & 1u);
   const int64_t h0 = first_win ? R.h0[r] : 0;
   const uint64_t a = win[lo];
-  const int64_t e = (int64_t)(i - a) + 1;
-  bool ex;
-  if (Lim < 0) ex = true;
-  else if (h0 > Lim) ex = e == 1 || (e - 1) % (Lim + 1) == 0;
-  else ex = (h0 + e) % (Lim + 1) == 0;
+  const bool ex = window_hits(h0, (int64_t)(i - a) + 1, Lim) == 0;
   const uint8_t first_mt = first_win ? (uint8_t)((fl >> 1) & 3u) : (uint8_t)BJX_OUTSIDE_INTERVAL;
   const uint8_t mt = (!cont && i == a) ? first_mt : (uint8_t)BJX_INSIDE_INTERVAL;
   const bool seen = rec[i].seen();
-  out_sorted[i] = (uint8_t)(0x80 | (seen ? 1 : 0) | (mt << 1) | (ex ? 8 : 0));
+  out_sorted[i] = outcome_byte(seen, mt, ex);
   if (R.wcnt) atomicAdd(&R.wcnt[i], 1u);
 }
 
@@ -6944,6 +7131,10 @@ static void rl_sort_apply(bjx_engine *e, const Bind &B, const EvSrc &E, uint64_t
   // 2 two-level whenever the table allows it (no batch-size gate, no hold)
   const char *s2 = getenv("BJX_SORT2");
   const int sort2 = s2 ? atoi(s2) : 1;
+  // BJX_WAVE_RUNS (test / timing hook, read per batch): 0 keeps every run of k_bucket_apply on
+  // its lane-per-run loop, N >= 2 moves the runs of at least N events to the wave-per-run path
+  const char *wr = getenv("BJX_WAVE_RUNS");
+  const uint32_t wave_min = !wr ? kWaveRun : atoi(wr) <= 0 ? 0xFFFFFFFFu : (uint32_t)std::max(2, atoi(wr));
   // two-level grouping (k_bucket_apply) unless the buckets would be too full on
   // average (then most of them would take the full path anyway); BJX_CHECK's
   // write accounting covers both paths
@@ -6990,11 +7181,21 @@ static void rl_sort_apply(bjx_engine *e, const Bind &B, const EvSrc &E, uint64_t
   } else {
     e->bk_start.ensure(nb + 1); e->bk_big.ensure(nb); e->bk_nbig.ensure(1);
     HIP_OK(hipMemsetAsync(e->bk_nbig.p, 0, 8, st));
-    hipLaunchKernelGGL(k_bucket_bounds, dim3(grid_for(n_ev + 1)), dim3(kBlock), 0, st, n_ev, e->ev_st2.p, (uint32_t)L, nb,
+    hipLaunchKernelGGL(k_bucket_bounds, dim3(grid_for(n_ev / 4 + 1)), dim3(kBlock), 0, st, n_ev, e->ev_st2.p, (uint32_t)L, nb,
                        e->bk_start.p);
     hipLaunchKernelGGL(k_bucket_apply<Rec>, dim3(nb), dim3(kBlock), 0, st, e->ev_st2.p, rec2, e->bk_start.p, (uint32_t)L, base,
-                       B.rules, e->S.st, e->ev_out_s.p, e->bk_big.p, e->bk_nbig.p, wcnt);
+                       B.rules, e->S.st, e->ev_out_s.p, e->bk_big.p, e->bk_nbig.p, wcnt, wave_min);
     HIP_OK(hipGetLastError());
+#ifdef BJX_BK_CENSUS
+    {
+      unsigned long long c[8], z[8] = {0};
+      HIP_OK(hipStreamSynchronize(st));
+      HIP_OK(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_bk_census), sizeof c));
+      HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(g_bk_census), z, sizeof z));
+      fprintf(stderr, "[bjx] bucket census: events %llu runs %llu; in runs >= 8: %llu / %llu, >= 16: %llu / %llu, >= 64: %llu / %llu\n",
+              c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]);
+    }
+#endif
     unsigned long long n_big = 0;
     pin_get(e, &n_big, e->bk_nbig.p, 8);
     pin_sync(e);
