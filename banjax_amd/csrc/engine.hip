@@ -73,6 +73,15 @@ __device__ __forceinline__ uint32_t nl_mask_word(uint32_t v) {
   uint32_t t = ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x;
   return ~t & 0x80808080u;
 }
+// 16-bit mask (bit i = byte i) of the 0x80 byte flags of four words, as
+// nl_mask_word and its kin return them: v_dot4_u32_u8 gathers a word's four
+// flags (weights 1, 2, 4, 8 on the first word of a pair, 16 .. 128 on the
+// second: the sum is 0x80 x the pair's 8-bit mask), one shift joins the pairs
+__device__ __forceinline__ uint32_t flag_mask16(uint32_t f0, uint32_t f1, uint32_t f2, uint32_t f3) {
+  const uint32_t a = __builtin_amdgcn_udot4(f1, 0x80402010u, __builtin_amdgcn_udot4(f0, 0x08040201u, 0u, false), false);
+  const uint32_t b = __builtin_amdgcn_udot4(f3, 0x80402010u, __builtin_amdgcn_udot4(f2, 0x08040201u, 0u, false), false);
+  return ((b << 8) | a) >> 7;
+}
 
 // --------------------------------------------------------------- lookups
 
@@ -590,14 +599,13 @@ constexpr uint32_t kSpanBytes = 12 * 1024;    // k_lines: bytes of 64 lines stag
 // 16-bit mask of the spaces among 16 bytes
 __device__ __forceinline__ uint32_t space_mask16(const uint4 v) {
   const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
-  uint32_t m16 = 0;
+  uint32_t hb[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const uint32_t x = wv[k] ^ 0x20202020u;
-    const uint32_t hb = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
-    m16 |= (((hb >> 7) & 1u) | ((hb >> 14) & 2u) | ((hb >> 21) & 4u) | ((hb >> 28) & 8u)) << (4 * k);
+    hb[k] = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
   }
-  return m16;
+  return flag_mask16(hb[0], hb[1], hb[2], hb[3]);
 }
 
 // 4 ASCII digits (first char lowest byte): exact test, and their value
@@ -658,14 +666,7 @@ __device__ __forceinline__ uint32_t find_spaces(const uint8_t *p, uint32_t n, ui
   for (uint32_t c = c0; c * 16 < n + skip && ns < 4; ++c) {
     const uint4 v = base[c];
     // 16-bit mask of the spaces of this chunk inside [p, p + n)
-    uint32_t m16 = 0;
-    const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t x = wv[k] ^ 0x20202020u;
-      const uint32_t hb = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
-      m16 |= (((hb >> 7) & 1u) | ((hb >> 14) & 2u) | ((hb >> 21) & 4u) | ((hb >> 28) & 8u)) << (4 * k);
-    }
+    uint32_t m16 = space_mask16(v);
     const int32_t lo = (int32_t)skip - (int32_t)(c * 16), hi = lo + (int32_t)n;  // valid chunk bytes [lo, hi)
     if (lo > 0) m16 &= ~((1u << lo) - 1u);
     if (hi < 16) m16 &= hi > 0 ? (1u << hi) - 1u : 0u;
@@ -2606,14 +2607,7 @@ __device__ __forceinline__ bool dfa_text(const Bind &B, const DevRule &R, const 
 // dfa_text over the text from t0 to the line's '\n' (a job window record,
 // kJob*): the end is found in the 16 B loads the automaton steps over anyway
 __device__ __forceinline__ uint32_t nl_mask16(const uint4 v) {
-  const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
-  uint32_t m = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const uint32_t hb = nl_mask_word(wv[q]);
-    m |= (((hb >> 7) & 1u) | ((hb >> 14) & 2u) | ((hb >> 21) & 4u) | ((hb >> 28) & 8u)) << (4 * q);
-  }
-  return m;
+  return flag_mask16(nl_mask_word(v.x), nl_mask_word(v.y), nl_mask_word(v.z), nl_mask_word(v.w));
 }
 template <bool STAGED>
 __device__ __forceinline__ bool dfa_line(const Bind &B, const DevRule &R, const uint16_t *tr, const uint8_t *ac,
@@ -7667,14 +7661,17 @@ static bool match_phase(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *byt
       HIP_OK(hipGetLastError());
 #ifdef BJX_PROF_L2
       {
-        unsigned long long c[8];
-        pin_get(e, c, e->chk.p, 64);
+        unsigned long long c[16];
+        pin_get(e, c, e->chk.p, 128);
         pin_sync(e);
         double tot = 0;
         for (int k = 0; k < 8; ++k) tot += (double)c[k];
         fprintf(stderr, "[bjx] k_lines2 segments (%% of wave clocks): loads %.1f header %.1f host+allow %.1f hits %.1f "
                 "anchored %.1f jobs %.1f stores %.1f flush %.1f\n", 100 * c[0] / tot, 100 * c[1] / tot, 100 * c[2] / tot,
                 100 * c[3] / tot, 100 * c[4] / tot, 100 * c[5] / tot, 100 * c[6] / tot, 100 * c[7] / tot);
+        fprintf(stderr, "[bjx] k_lines2 census of %llu lines, lines / 64-line trips: header past the window %llu / %llu, "
+                "check from HBM %llu / %llu, anchored entry from HBM %llu / %llu, unverified hit from HBM %llu / %llu\n",
+                (unsigned long long)n_lines, c[8], c[9], c[10], c[11], c[12], c[13], c[14], c[15]);
       }
 #endif
     } else {

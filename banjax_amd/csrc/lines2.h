@@ -7,7 +7,9 @@
 // Window: each lane copies the 16 B-aligned 112 bytes that hold its line's
 // first bytes into its own LDS window (7 x 16 B loads, 7 ds_write_b128); the
 // header, the anchored windows at the start of rest and the template / literal
-// checks around hits read it there, anything past it from HBM.  112 B = 28
+// checks around hits read it there, hits and checks past it from HBM.  The
+// header (through the fourth space) is read from the window only: a line whose
+// header runs past it goes to the per-line fallback.  112 B = 28
 // dwords per lane (an odd multiple of 4): lanes reading the same window offset
 // with ds_read_b128 hit distinct banks.
 //
@@ -114,10 +116,12 @@ __device__ __forceinline__ void l2_take_spaces(uint64_t m, int32_t base, uint32_
   }
 }
 
-// first four spaces of line bytes [0, n): the window (line byte o at win[sk +
-// o]) 64 bytes at a time, then HBM past it (gp = line start)
-__device__ __forceinline__ uint32_t l2_spaces(const uint8_t *win, uint32_t sk, const uint8_t *gp, uint32_t n, uint32_t &sp0,
-                                              uint32_t &sp1, uint32_t &sp2, uint32_t &sp3) {
+// first four spaces of the line bytes [0, n) that lie in the window (line
+// byte o at win[sk + o]), 64 bytes at a time; fewer than four of a line that
+// runs past the window: its header is not in the window (the per-line fallback
+// takes the line)
+__device__ __forceinline__ uint32_t l2_spaces(const uint8_t *win, uint32_t sk, uint32_t n, uint32_t &sp0, uint32_t &sp1,
+                                              uint32_t &sp2, uint32_t &sp3) {
   const uint4 *w = reinterpret_cast<const uint4 *>(win);
   uint32_t ns = 0;
   {
@@ -133,22 +137,6 @@ __device__ __forceinline__ uint32_t l2_spaces(const uint8_t *win, uint32_t sk, c
     uint64_t m = (uint64_t)space_mask16(v4) | ((uint64_t)space_mask16(v5) << 16) | ((uint64_t)space_mask16(v6) << 32);
     if (sk + n < kL2Win) m &= (1ull << (sk + n - 64)) - 1ull;
     l2_take_spaces(m, 64 - (int32_t)sk, ns, sp0, sp1, sp2, sp3);
-  }
-  const uint32_t lim = kL2Win - sk;
-  if (ns < 4 && n > lim) {  // a header longer than the window: the rest from HBM
-    uint32_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;
-    const uint32_t nq = find_spaces(gp + lim, n - lim, q0, q1, q2, q3);
-    const uint32_t q[4] = {q0, q1, q2, q3};
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) {
-      const bool has = k < nq && ns < 4;
-      const uint32_t pos = q[k] + lim;
-      sp0 = has && ns == 0 ? pos : sp0;
-      sp1 = has && ns == 1 ? pos : sp1;
-      sp2 = has && ns == 2 ? pos : sp2;
-      sp3 = has && ns == 3 ? pos : sp3;
-      ns += has ? 1u : 0u;
-    }
   }
   return ns;
 }
@@ -401,6 +389,8 @@ __global__ __launch_bounds__(kL2Block, 4) void k_lines2(Bind B, LinesArgs A) {
 #ifdef BJX_PROF_L2
   LinesProf P;
   P.start();
+  // census of the lines (even slots) and waves (odd) that take each HBM-side variant
+  unsigned long long cen[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
   for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x + wave * 64u; base < A.n_lines; base += stride) {
     const uint64_t j = base + lane;
@@ -417,9 +407,26 @@ __global__ __launch_bounds__(kL2Block, 4) void k_lines2(Bind B, LinesArgs A) {
     // ---- the line's window: 16 B-aligned pieces from its first byte
     const uint64_t a0 = s & ~15ull;
     const uint32_t sk = (uint32_t)(s - a0);
-    {
-      uint4 v[kL2Win / 16];
+    // every window of the wave ends inside the batch (all waves but the one
+    // with the batch's last lines): one test per wave, loads without bounds
+    const bool full = __ballot(a0 + kL2Win > A.n) == 0;
+    // the hit slots the scan filled (most lines have none or one: 16 B, not 32)
+    auto load_cands = [&]() __attribute__((always_inline)) {
+      if (act && B.any_prefilter && cm.cnt) {
+        const ulonglong2 *cp = reinterpret_cast<const ulonglong2 *>(L.cand + j * kCandSlots);
+        const ulonglong2 w0 = cp[0];
+        cv[0] = w0.x;
+        cv[1] = w0.y;
+        if (cm.cnt > 2) {
+          const ulonglong2 w1 = cp[1];
+          cv[2] = w1.x;
+          cv[3] = w1.y;
+        }
+      }
+    };
+    if (__builtin_expect(full, 1)) {
 #ifdef BJX_L2_TLOAD
+      uint4 v[kL2Win / 16];
       // the wave's 64 windows as 448 pieces of 16 B, piece g = 7 line + k at
       // wbase + 16 g: in step k lane l loads piece 64 k + l, so consecutive
       // lanes read consecutive 16 B of one line (about 9 lines, 18 cache lines
@@ -432,48 +439,46 @@ __global__ __launch_bounds__(kL2Block, 4) void k_lines2(Bind B, LinesArgs A) {
         const uint32_t g = 64u * k + lane;
         const uint32_t ln = (g * 9363u) >> 16;  // g / 7 for g < 448
         const uint64_t a = w0 + __shfl(rel, (int)ln) + 16ull * (g - 7u * ln);
-#else
-#pragma unroll
-      for (uint32_t k = 0; k < kL2Win / 16; ++k) {
-        const uint64_t a = a0 + 16ull * k;
-#endif
-        if (a + 16 <= A.n) v[k] = *reinterpret_cast<const uint4 *>(A.buf + a);
-        else {
-          uint32_t w4[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            uint32_t x = 0;
-            for (int bb = 0; bb < 4; ++bb) {
-              const uint64_t p = a + 4 * q + bb;
-              if (p < A.n) x |= (uint32_t)A.buf[p] << (8 * bb);
-            }
-            w4[q] = x;
-          }
-          v[k] = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-        }
+        v[k] = *reinterpret_cast<const uint4 *>(A.buf + a);
       }
-      // the hit slots the scan filled (most lines have none or one: 16 B, not 32)
-      if (act && B.any_prefilter && cm.cnt) {
-        const ulonglong2 *cp = reinterpret_cast<const ulonglong2 *>(L.cand + j * kCandSlots);
-        const ulonglong2 w0 = cp[0];
-        cv[0] = w0.x;
-        cv[1] = w0.y;
-        if (cm.cnt > 2) {
-          const ulonglong2 w1 = cp[1];
-          cv[2] = w1.x;
-          cv[3] = w1.y;
-        }
-      }
-#ifdef BJX_L2_TLOAD
+      load_cands();
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (uint32_t k = 0; k < kL2Win / 16; ++k) reinterpret_cast<uint4 *>(wbase)[64u * k + lane] = v[k];
-      wave_sync();  // every lane reads the window its neighbours wrote
 #else
-#pragma unroll
-      for (uint32_t k = 0; k < kL2Win / 16; ++k) reinterpret_cast<uint4 *>(win)[k] = v[k];
+      // (named values, not an array: no alloca for the optimiser to leave in scratch)
+      const uint4 *src = reinterpret_cast<const uint4 *>(A.buf + a0);
+      const uint4 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3], v4 = src[4], v5 = src[5], v6 = src[6];
+      load_cands();
+      // all seven loads in flight before the first LDS write waits for one: left
+      // to itself the scheduler saves registers by pairing each load with its
+      // write, seven HBM round trips in a row
+      __builtin_amdgcn_sched_barrier(0);
+      uint4 *dst = reinterpret_cast<uint4 *>(win);
+      dst[0] = v0, dst[1] = v1, dst[2] = v2, dst[3] = v3, dst[4] = v4, dst[5] = v5, dst[6] = v6;
 #endif
+    } else {
+      // the batch's last wave: each lane its own window a byte at a time,
+      // bytes past the batch read as 0 (a rolled loop: small, cold code)
+      load_cands();
+#pragma nounroll
+      for (uint32_t q = 0; q < kL2Win / 4; ++q) {
+        uint32_t x = 0;
+#pragma nounroll
+        for (uint32_t bb = 0; bb < 4; ++bb) {
+          const uint64_t p = a0 + 4 * q + bb;
+          if (p < A.n) x |= (uint32_t)A.buf[p] << (8 * bb);
+        }
+        reinterpret_cast<uint32_t *>(win)[q] = x;
+      }
     }
+#ifdef BJX_L2_TLOAD
+    wave_sync();  // every lane reads the window its neighbours wrote
+#endif
     L2P(0);
+#ifdef BJX_PROF_L2
+    uint32_t cz = 0;  // census: 1 header past the window, 2 check, 4 anchored entry, 8 unverified hit read from HBM
+#endif
     if (act) {
       L2Line X;
       X.wp = win + sk;
@@ -481,31 +486,38 @@ __global__ __launch_bounds__(kL2Block, 4) void k_lines2(Bind B, LinesArgs A) {
       X.lim = kL2Win - sk;
       X.n = n;
       uint32_t sp0 = 0, sp1 = 0, sp2 = 0, sp3 = 0;
-      const uint32_t ns = l2_spaces(win, sk, X.gp, n, sp0, sp1, sp2, sp3);
+      const uint32_t ns = l2_spaces(win, sk, n, sp0, sp1, sp2, sp3);
       double f = 0.0;
-      bool slow = false;
+      // a header (through its fourth space) that runs past the window, or an
+      // exotic timestamp token: the per-line fallback parses the line from HBM.
+      // Every other line's timestamp, IP and host fields lie in the window.
+      bool slow = ns < 4 && n > X.lim;
       if (ns >= 4) slow = parse_ts_msec(X.wp, sp0, &f) != 0 && parse_float_fast(X.wp, sp0, &f) != 0;
       L2P(1);
-      if (ns < 4) {
+#ifdef BJX_PROF_L2
+      if (ns < 4 && n > X.lim) cz |= 1u;
+#endif
+      if (ns < 4 && !slow) {
         L.flags[j] = kLineError;
         L.counts[j] = 0;
-      } else if (slow) {  // exotic timestamp token: the per-line fallback
+      } else if (slow) {
         L.flags[j] = kLineSlowTs;
         L.counts[j] = 0;
         push_list(A.slow_list, A.slow_count, j);
       } else {
         const uint32_t ip_off = sp0 + 1, ip_len = sp1 - sp0 - 1;
         const uint32_t rest_off = sp1 + 1, host_off = sp2 + 1, host_len = sp3 - sp2 - 1;
-        const bool hostw = l2_in(X, host_off, host_len);
-        const int32_t hid = hostw ? host_lookup_lds(s_hl, X.wp + host_off, host_len)
-                                  : host_lookup_lds(s_hl, X.gp + host_off, host_len);
+        // the host and the IP end before the fourth space, inside the window:
+        // a word read that straddles their end stays in the wave's LDS, and
+        // its bytes past the field are masked off or not used
+        const int32_t hid = host_lookup_lds(s_hl, X.wp + host_off, host_len);
         const uint32_t dc = hid >= 0 ? s_hl[B.l2_hdc + (uint32_t)hid] : B.l2_none;
         const uint32_t dw = B.l2_dcls + dc * DW;
         const uint32_t rows = s_hl[dw + 10 * W], prule = s_hl[dw + 10 * W + 1], anc = s_hl[dw + 10 * W + 2],
                        n_anc = s_hl[dw + 10 * W + 3];
         const uint32_t first_rule = hid >= 0 ? LT.hinfo[hid].y : 0u;
         const uint32_t pinl = s_hl[dw + 10 * W + 4];  // the class's inline-DFA entries per position (0: none)
-        const bool exempt = B.any_allow && check_is_allowed(B, hid, X.gp + ip_off, ip_len);
+        const bool exempt = B.any_allow && check_is_allowed(B, hid, X.wp + ip_off, ip_len);
         L2P(2);
         const int64_t tsn = ns_from_seconds(f);
         uint8_t fl = 0;
@@ -538,6 +550,9 @@ __global__ __launch_bounds__(kL2Block, 4) void k_lines2(Bind B, LinesArgs A) {
             if (!(v & kCandVerified)) {
               const uint32_t o = (uint32_t)(q - s), ll = lit_len_of(TB, lit);
               if (o + ll > n) continue;
+#ifdef BJX_PROF_L2
+              if (!l2_in(X, o, ll)) cz |= 8u;
+#endif
               if (!(l2_in(X, o, ll) ? literal_at(TB, lit, X.wp + o) : literal_at(TB, lit, X.gp + o))) continue;
             }
             if (lit < 32) ovbits |= 1u << lit;
@@ -558,7 +573,10 @@ __global__ __launch_bounds__(kL2Block, 4) void k_lines2(Bind B, LinesArgs A) {
                 // in the window: the checked text (ck.w bytes from the hit, plus the
                 // host for a template that spells it after the hit) and the host field
                 const uint32_t tail = ck.w + (((ck.x >> 11) & 1u) ? host_len : 0u);
-                const bool inw = hostw && rest_off + hp + tail + 8 <= X.lim;
+                const bool inw = rest_off + hp + tail + 8 <= X.lim;
+#ifdef BJX_PROF_L2
+                if (!inw) cz |= 2u;
+#endif
                 out = inw ? l2_check<true>(TB, LT, ck, X.wp + rest_off, rest_len, host_rel, host_len, hp)
                           : l2_check<false>(TB, LT, ck, X.gp + rest_off, rest_len, host_rel, host_len, hp);
               }
@@ -601,7 +619,10 @@ __global__ __launch_bounds__(kL2Block, 4) void k_lines2(Bind B, LinesArgs A) {
             // in the window: the bytes of rest the entry may read (ext, plus the
             // host for a template) and the host field
             const uint32_t need = (ext & 0x7FFFFFFFu) + ((ext >> 31) ? host_len : 0u);
-            const bool inw = hostw && rest_off + need + 8 <= X.lim;
+            const bool inw = rest_off + need + 8 <= X.lim;
+#ifdef BJX_PROF_L2
+            if (!inw) cz |= 4u;
+#endif
             const uint32_t out = inw ? l2_anchored<true>(B, TB, LT, a, bq, r, X.wp + rest_off, rest_len, host_rel, host_len)
                                      : l2_anchored<false>(B, TB, LT, a, bq, r, X.gp + rest_off, rest_len, host_rel, host_len);
             if (out == 1) l2_set(m, pos);
@@ -656,8 +677,7 @@ __global__ __launch_bounds__(kL2Block, 4) void k_lines2(Bind B, LinesArgs A) {
         if (evl && !(A.dbg2 & 8)) {
           uint4 k16;
           uint64_t h;
-          if (l2_in(X, ip_off, ip_len > 16 ? ip_len : 16u)) ip_key_hash(X.wp + ip_off, ip_len, k16, h);
-          else ip_key_hash(X.gp + ip_off, ip_len, k16, h);
+          ip_key_hash(X.wp + ip_off, ip_len, k16, h);
           if (ip_len > 15) L.ip_hash[j] = h;
           L.ip16[j] = k16;
         }
@@ -669,10 +689,20 @@ __global__ __launch_bounds__(kL2Block, 4) void k_lines2(Bind B, LinesArgs A) {
     // ---- append this wave's DFA jobs (from its chunk of the job array)
     flush_jobs(S, JC, lane);
     L2P(7);
+#ifdef BJX_PROF_L2
+    for (int k = 0; k < 4; ++k) {
+      const uint64_t bm = __ballot((cz >> k) & 1u);
+      cen[2 * k] += __popcll(bm);
+      cen[2 * k + 1] += bm != 0;
+    }
+#endif
   }
   close_jobs(S, JC, lane, A.null_key, A.job_real);
 #ifdef BJX_PROF_L2
   if (lane == 0 && A.prof)
-    for (int k = 0; k < 8; ++k) atomicAdd(&A.prof[k], (unsigned long long)P.acc[k]);
+    for (int k = 0; k < 8; ++k) {
+      atomicAdd(&A.prof[k], (unsigned long long)P.acc[k]);
+      atomicAdd(&A.prof[8 + k], cen[k]);
+    }
 #endif
 }
