@@ -108,6 +108,8 @@ EXPORTS = [
     "bjx_node_set_ban_options", "bjx_node_process_batch", "bjx_node_process_chunks", "bjx_node_batch_bans",
     "bjx_node_state_get", "bjx_node_state_len", "bjx_node_state_dump", "bjx_node_state_stats_get",
     "bjx_node_state_clear", "bjx_node_exchange_kind", "bjx_state_expire", "bjx_node_state_expire",
+    "bjx_state_export_bound", "bjx_state_export", "bjx_state_import",
+    "bjx_node_state_export_bound", "bjx_node_state_export", "bjx_node_state_import",
 ]
 
 
@@ -121,6 +123,12 @@ class ExpireStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("states_before", "states_dropped", "ips_before", "ips_dropped",
                                             "arena_bytes_before", "arena_bytes_after", "device_bytes_before",
                                             "device_bytes_after")] + [("device_ms", C.c_double)]
+
+
+class SnapshotStats(C.Structure):
+    """bjx_snapshot_stats: what one bjx_state_export / bjx_state_import moved."""
+    _fields_ = [(k, C.c_uint64) for k in ("ips", "states", "names", "bytes", "ips_skipped", "states_skipped")] + \
+               [("device_ms", C.c_double)]
 
 
 _lib = None
@@ -264,6 +272,15 @@ def lib():
     L.bjx_state_expire.argtypes = [vp, C.c_int64, C.POINTER(ExpireStats)]
     L.bjx_node_state_expire.restype = C.c_int
     L.bjx_node_state_expire.argtypes = [vp, C.c_int64, C.POINTER(ExpireStats)]
+    for pre in ("bjx_state", "bjx_node_state"):
+        f = getattr(L, pre + "_export_bound")
+        f.restype, f.argtypes = C.c_uint64, [vp]
+        f = getattr(L, pre + "_export")
+        f.restype, f.argtypes = C.c_int, [vp, C.c_int64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(SnapshotStats)]
+    L.bjx_state_import.restype = C.c_int
+    L.bjx_state_import.argtypes = [vp, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(SnapshotStats)]
+    L.bjx_node_state_import.restype = C.c_int
+    L.bjx_node_state_import.argtypes = [vp, C.c_char_p, C.c_uint64, C.POINTER(SnapshotStats)]
     _lib = L
     return L
 

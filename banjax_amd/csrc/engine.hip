@@ -42,6 +42,7 @@
 #include "engine_types.h"
 #include "regex_compiler.h"
 #include "bans.h"
+#include "snapshot.h"
 
 using namespace bjx;
 
@@ -4612,6 +4613,207 @@ __global__ void k_exp_counters(uint64_t *__restrict__ counters, uint64_t ips, ui
   counters[2] = states;
 }
 
+// snapshot export (bjx_state_export; format: snapshot.h).  keep / nid / noff
+// come from expiry's mark, length and scan passes with min_start_ns as the
+// cutoff.  k_snap_compact gathers the surviving slots, in any order, as
+// (key = new IP id << 24 | name id, index, {hits, start}) and marks the name
+// ids in use; the host sorts the used names and k_snap_remap rewrites the name
+// bits to the canonical index; a radix sort over the key bits in use orders the
+// records by (ip, name); k_snap_gather writes them, k_snap_ips the IP section.
+// One atomic per block and pass (block_alloc); every block runs the same
+// number of passes.
+__global__ __launch_bounds__(kBlock) void k_snap_compact(uint64_t st_cap, const StSlot *__restrict__ st, int64_t cutoff,
+                                                         uint64_t n_ips, const uint32_t *__restrict__ nid, uint32_t n_names,
+                                                         uint32_t *__restrict__ used, unsigned long long *__restrict__ ctr,
+                                                         uint64_t room, uint64_t *__restrict__ keys,
+                                                         uint32_t *__restrict__ idx, int64_t *__restrict__ pay) {
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < st_cap; base += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t i = base + threadIdx.x;
+    StSlot v{};
+    bool live = false;
+    if (i < st_cap) {
+      v = st[i];
+      live = st_survives(v, cutoff, n_ips) && (v.key & 0xFFFFFFull) < n_names;
+    }
+    const uint64_t k = block_alloc(ctr, live ? 1 : 0);
+    if (live && k < room) {
+      const uint32_t name = (uint32_t)(v.key & 0xFFFFFFull);
+      used[name] = 1u;  // every writer stores the same value
+      keys[k] = ((uint64_t)nid[(v.key >> 24) - 1] << 24) | name;
+      idx[k] = (uint32_t)k;
+      pay[2 * k] = v.hits;
+      pay[2 * k + 1] = v.start;
+    }
+  }
+}
+__global__ void k_snap_remap(uint64_t n, uint64_t *__restrict__ keys, const uint32_t *__restrict__ remap) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const uint64_t v = keys[k];
+  keys[k] = (v & ~0xFFFFFFull) | remap[v & 0xFFFFFFull];
+}
+// sorted (key, index) -> the 24-byte record {u32 ip, u32 name, i64 hits, i64 start} as three words
+__global__ void k_snap_gather(uint64_t n, const uint64_t *__restrict__ keys, const uint32_t *__restrict__ idx,
+                              const int64_t *__restrict__ pay, uint64_t *__restrict__ recs) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const uint64_t key = keys[j], s = idx[j];
+  if (s >= n) return;  // (a permutation of [0, n): never taken)
+  recs[3 * j] = (key >> 24) | ((key & 0xFFFFFFull) << 32);
+  recs[3 * j + 1] = (uint64_t)pay[2 * s];
+  recs[3 * j + 2] = (uint64_t)pay[2 * s + 1];
+}
+// kept IP id -> its bytes and offset under the new id (k_exp_arena's shape); i = n_ips writes the end offset
+__global__ void k_snap_ips(uint64_t n_ips, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ nid,
+                           const uint64_t *__restrict__ noff, const uint64_t *__restrict__ o_off,
+                           const uint32_t *__restrict__ o_len, const uint8_t *__restrict__ o_arena, uint64_t o_used,
+                           uint64_t kept_ips, uint64_t kept_bytes, uint64_t *__restrict__ out_off,
+                           uint8_t *__restrict__ out_bytes) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n_ips) return;
+  if (i == n_ips) { out_off[kept_ips] = kept_bytes; return; }
+  if (!keep[i]) return;
+  const uint32_t len = o_len[i];
+  const uint64_t so = o_off[i], d = noff[i];
+  if (so + len > o_used || d + len > kept_bytes || nid[i] >= kept_ips) return;  // (not from a finished batch)
+  for (uint32_t k = 0; k < len; ++k) out_bytes[d + k] = o_arena[so + k];
+  out_off[nid[i]] = d;
+}
+
+// snapshot import (bjx_state_import).  err[c] = 1 (plain stores of one value)
+// when check c fails: 1 ip_off not monotone from 0, 2 ip_off[n_ips] !=
+// ip_bytes, 3 record ip >= n_ips, 4 record name >= n_names, 5 records not
+// strictly ascending, 6 an IP without a record (the records are sorted by IP,
+// so that is a first IP other than 0, a step over an index, or a last IP other
+// than n_ips - 1), 0 (k_imp_verify) an IP found twice or not under its own id.
+__global__ void k_imp_check(uint64_t n_ips, const uint64_t *__restrict__ ip_off, uint64_t ip_bytes, uint64_t n_states,
+                            const uint64_t *__restrict__ recs, uint32_t n_names, uint32_t *__restrict__ used,
+                            uint32_t *__restrict__ err) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i <= n_ips) {
+    const uint64_t a = ip_off[i];
+    if (i == 0 && a != 0) err[1] = 1u;
+    if (i == n_ips) {
+      if (a != ip_bytes) err[2] = 1u;
+    } else {
+      const uint64_t b = ip_off[i + 1];
+      if (b < a || b - a > 0x7FFFFFFFull) err[1] = 1u;
+    }
+  }
+  if (i < n_states) {
+    const uint64_t w = recs[3 * i];
+    const uint32_t ip = (uint32_t)w, nm = (uint32_t)(w >> 32);
+    if (ip >= n_ips) err[3] = 1u;
+    if (nm >= n_names) err[4] = 1u;
+    else used[nm] = 1u;
+    if (i) {
+      const uint64_t pw = recs[3 * (i - 1)];
+      const uint32_t pip = (uint32_t)pw, pnm = (uint32_t)(pw >> 32);
+      if (ip < pip || (ip == pip && nm <= pnm)) err[5] = 1u;
+      else if (ip - pip > 1) err[6] = 1u;
+    } else if (ip != 0) {
+      err[6] = 1u;
+    }
+    if (i == n_states - 1 && (uint64_t)ip + 1 != n_ips) err[6] = 1u;
+  }
+}
+// per IP: hash_bytes of its bytes, the owner filter, the arena bytes it keeps ([0, n_ips]: the last entry 0)
+__global__ void k_imp_ip(uint64_t n_ips, const uint64_t *__restrict__ ip_off, const uint8_t *__restrict__ bytes,
+                         uint32_t part, uint32_t n_parts, uint32_t *__restrict__ keep, uint64_t *__restrict__ klen,
+                         uint64_t *__restrict__ hash) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n_ips) return;
+  if (i == n_ips) { keep[i] = 0; klen[i] = 0; hash[i] = 0; return; }
+  const uint64_t a = ip_off[i];
+  const uint32_t len = (uint32_t)(ip_off[i + 1] - a);
+  const uint64_t h = hash_bytes(bytes + a, len);
+  const bool mine = (uint32_t)((h >> 32) % n_parts) == part;  // the node's owner function (part_line)
+  keep[i] = mine ? 1u : 0u;
+  klen[i] = mine ? len : 0;
+  hash[i] = h;
+}
+// cnt[0] += records of kept IPs (one atomic per block)
+__global__ __launch_bounds__(kBlock) void k_imp_count(uint64_t n_states, const uint64_t *__restrict__ recs,
+                                                      const uint32_t *__restrict__ keep,
+                                                      unsigned long long *__restrict__ cnt) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t n = i < n_states && keep[(uint32_t)recs[3 * i]] ? 1 : 0, z = 0;
+  block_sum2(n, z);
+  if (threadIdx.x == 0 && n) atomicAdd(&cnt[0], (unsigned long long)n);
+}
+// kept IP -> arena bytes, offset, length and its IpSlot (CAS on an empty slot,
+// as k_exp_ip: equal hashes of distinct IPs take successive slots)
+__global__ void k_imp_place(uint64_t n_ips, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ nid,
+                            const uint64_t *__restrict__ noff, const uint64_t *__restrict__ hash, uint64_t hmask,
+                            const uint64_t *__restrict__ ip_off, const uint8_t *__restrict__ bytes, uint32_t born,
+                            uint64_t kept_ips, uint8_t *__restrict__ n_arena, uint64_t n_arena_cap,
+                            uint64_t *__restrict__ n_off, uint32_t *__restrict__ n_len, IpSlot *__restrict__ nt,
+                            uint64_t nmask) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_ips || !keep[i]) return;
+  const uint64_t a = ip_off[i], d = noff[i];
+  const uint32_t len = (uint32_t)(ip_off[i + 1] - a), id = nid[i];
+  if (id >= kept_ips || d + len > n_arena_cap) return;  // (the scans' totals sized both: never taken)
+  const uint8_t *src = bytes + a;
+  for (uint32_t k = 0; k < len; ++k) n_arena[d + k] = src[k];
+  n_off[id] = d;
+  n_len[id] = len;
+  const uint64_t h = hmask ? (hash[i] & hmask) | 1ull : hash[i];
+  uint64_t j = h & nmask;
+  for (;;) {
+    const unsigned long long prev = atomicCAS((unsigned long long *)&nt[j].hash, 0ull, (unsigned long long)h);
+    if (prev == 0) { nt[j].id = id; nt[j].born = born; nt[j].key16 = ip_key16_bytes(src, len); return; }
+    j = (j + 1) & nmask;
+  }
+}
+// one lane per record of a kept IP (CAS on the key, as k_exp_st)
+__global__ void k_imp_st(uint64_t n_states, const uint64_t *__restrict__ recs, const uint32_t *__restrict__ keep,
+                         const uint32_t *__restrict__ nid, const uint32_t *__restrict__ remap, StSlot *__restrict__ nt,
+                         uint64_t nmask) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_states) return;
+  const uint64_t w = recs[3 * i];
+  const uint32_t ip = (uint32_t)w;
+  if (!keep[ip]) return;
+  const uint64_t key = ((uint64_t)(nid[ip] + 1) << 24) | remap[w >> 32];
+  uint64_t j = mix64(key) & nmask;
+  for (;;) {
+    const unsigned long long prev = atomicCAS((unsigned long long *)&nt[j].key, 0ull, (unsigned long long)key);
+    if (prev == 0) { nt[j].hits = (int64_t)recs[3 * i + 1]; nt[j].start = (int64_t)recs[3 * i + 2]; nt[j].valid = 1; return; }
+    j = (j + 1) & nmask;
+  }
+}
+// every imported IP looked up as ip_claim_line looks up an IP of an earlier
+// batch (hash, key16, arena bytes past 15), along its whole probe chain: it
+// must match one slot, the one with its own id
+__global__ void k_imp_verify(uint64_t n_ips, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ nid,
+                             const uint64_t *__restrict__ hash, uint64_t hmask, const uint64_t *__restrict__ ip_off,
+                             const uint8_t *__restrict__ bytes, uint64_t kept_ips, const IpSlot *__restrict__ nt,
+                             uint64_t nmask, const uint64_t *__restrict__ n_off, const uint32_t *__restrict__ n_len,
+                             const uint8_t *__restrict__ n_arena, uint32_t *__restrict__ err) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_ips || !keep[i]) return;
+  const uint64_t a = ip_off[i];
+  const uint32_t len = (uint32_t)(ip_off[i + 1] - a);
+  const uint8_t *src = bytes + a;
+  const uint4 k16 = ip_key16_bytes(src, len);
+  const uint64_t h = hmask ? (hash[i] & hmask) | 1ull : hash[i];
+  uint32_t found = 0;
+  bool own = false;
+  uint64_t j = h & nmask;
+  for (uint64_t step = 0; step <= nmask; ++step) {
+    const IpSlot v = nt[j];
+    if (v.hash == 0) break;
+    if (v.hash == h && v.id < kept_ips && key16_eq(v.key16, k16) &&
+        (len <= 15 || (n_len[v.id] == len && bytes_eq(n_arena + n_off[v.id], src, len)))) {
+      ++found;
+      own = own || v.id == nid[i];
+    }
+    j = (j + 1) & nmask;
+  }
+  if (found != 1 || !own) err[0] = 1u;
+}
+
 // --------------------------------------------------------------- multi-GPU exchange
 // The partition runs over the lines in tiles of `steps` x kBlock lines (one
 // block each, one line per lane per step), in line order: k_part_count sums
@@ -5376,6 +5578,7 @@ struct bjx_engine {
   DevBuf<uint64_t> d_trips_c;
   HostBuf<bjx_rule_result> results;
   HostBuf<uint8_t> line_flags;
+  HostBuf<uint8_t> snap_pin;  // bjx_state_export / bjx_state_import: two pinned chunks the blob moves through
 };
 
 namespace {
@@ -7009,6 +7212,7 @@ extern "C" void bjx_engine_destroy(bjx_engine *e) {
   e->d_results.release(); e->q_out.release();
   e->ban_ips.release(); e->ban_log.release(); e->ban_off.release(); e->ban_kind.release(); e->ban_ipb.release();
   e->ban_ipo.release();
+  e->snap_pin.release();
   e->l_ip16.release(); e->jline.release(); e->jkey.release(); e->jidx.release(); e->jidx2.release(); e->jrec.release(); e->jkey2.release(); e->l_cand.release(); e->l_ccnt.release(); e->l_cfirst.release();
   (void)hipEventDestroy(e->ev0); (void)hipEventDestroy(e->ev1); (void)hipEventDestroy(e->evm0); (void)hipEventDestroy(e->evm1);
   for (auto &x : e->evk) (void)hipEventDestroy(x);
@@ -8870,6 +9074,386 @@ extern "C" int bjx_state_expire(bjx_engine *e, int64_t cutoff_ns, bjx_expire_sta
       out->device_bytes_before = bytes_before;
       out->device_bytes_after = state_device_bytes(ip_cap, st_cap, arena_cap);
       out->device_ms = (double)a + (double)b;
+    }
+    return BJX_OK;
+  } catch (const BjxError &x) {
+    e->last_error = x.what();
+    return x.code;
+  } catch (const std::bad_alloc &) {
+    e->last_error = "host out of memory";
+    return BJX_ERR_NOMEM;
+  }
+}
+
+// ---- snapshot: bjx_state_export / bjx_state_import (format and host checks: snapshot.h)
+namespace {
+struct SnapEvents {
+  hipEvent_t ev[8] = {};
+  void create() {
+    for (auto &x : ev) HIP_OK(hipEventCreate(&x));
+  }
+  ~SnapEvents() {
+    for (auto &x : ev)
+      if (x) (void)hipEventDestroy(x);
+  }
+  double ms(int a, int b) {
+    float t = 0;
+    HIP_OK(hipEventElapsedTime(&t, ev[a], ev[b]));
+    return (double)t;
+  }
+};
+constexpr size_t kSnapChunk = 8u << 20;
+// device memory <-> the caller's in chunks through two pinned buffers, the copy
+// of one chunk running while the host moves the other
+void snap_copy_out(bjx_engine *e, uint8_t *dst, const uint8_t *d_src, uint64_t n) {
+  e->snap_pin.reserve(2 * kSnapChunk);
+  SnapEvents E;
+  E.create();
+  const uint64_t nc = (n + kSnapChunk - 1) / kSnapChunk;
+  auto land = [&](uint64_t c) {
+    HIP_OK(hipEventSynchronize(E.ev[c & 1]));
+    memcpy(dst + c * kSnapChunk, e->snap_pin.p + (c & 1) * kSnapChunk, (size_t)std::min<uint64_t>(kSnapChunk, n - c * kSnapChunk));
+  };
+  for (uint64_t c = 0; c < nc; ++c) {
+    HIP_OK(hipMemcpyAsync(e->snap_pin.p + (c & 1) * kSnapChunk, d_src + c * kSnapChunk,
+                          (size_t)std::min<uint64_t>(kSnapChunk, n - c * kSnapChunk), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipEventRecord(E.ev[c & 1], e->stream));
+    if (c) land(c - 1);
+  }
+  if (nc) land(nc - 1);
+}
+void snap_copy_in(bjx_engine *e, uint8_t *d_dst, const uint8_t *src, uint64_t n) {
+  e->snap_pin.reserve(2 * kSnapChunk);
+  SnapEvents E;
+  E.create();
+  const uint64_t nc = (n + kSnapChunk - 1) / kSnapChunk;
+  for (uint64_t c = 0; c < nc; ++c) {
+    const size_t m = (size_t)std::min<uint64_t>(kSnapChunk, n - c * kSnapChunk);
+    if (c >= 2) HIP_OK(hipEventSynchronize(E.ev[c & 1]));  // the chunk that used this buffer has left it
+    memcpy(e->snap_pin.p + (c & 1) * kSnapChunk, src + c * kSnapChunk, m);
+    HIP_OK(hipMemcpyAsync(d_dst + c * kSnapChunk, e->snap_pin.p + (c & 1) * kSnapChunk, m, hipMemcpyHostToDevice, e->stream));
+    HIP_OK(hipEventRecord(E.ev[c & 1], e->stream));
+  }
+  HIP_OK(hipStreamSynchronize(e->stream));
+}
+}  // namespace
+
+extern "C" uint64_t bjx_state_export_bound(bjx_engine *e) {
+  if (!e) return 0;
+  std::lock_guard<std::mutex> g(e->mu);
+  try {
+    HIP_OK(hipSetDevice(e->device));
+    read_counters(e);
+    uint64_t nb = 0;
+    for (auto &x : e->names) nb += x.size();
+    bjx_snap::Layout L;
+    const char *why = nullptr;
+    if (!bjx_snap::make_layout(e->names.size(), nb, e->host_counters[0], e->host_counters[1], e->host_counters[2], &L, &why)) {
+      e->last_error = std::string("bjx_state_export_bound: ") + why;
+      return 0;
+    }
+    return L.total;
+  } catch (const BjxError &x) {
+    e->last_error = x.what();
+    return 0;
+  }
+}
+
+// Export: expiry's mark / scan passes with min_start_ns as the cutoff, then
+// the records compacted, sorted by (ip, name) and written with the IP section
+// into one device buffer laid out as the snapshot's tail, which is copied out.
+// The tables are only read.
+extern "C" int bjx_state_export(bjx_engine *e, int64_t min_start_ns, uint8_t *out, uint64_t cap, uint64_t *len,
+                                bjx_snapshot_stats *stats) {
+  if (!e) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  try {
+    if (len) *len = 0;
+    if (cap && !out) throw BjxError(BJX_ERR_ARG, "bjx_state_export: no output buffer");
+    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_export between bjx_match_batch and its bjx_finish_batch");
+    HIP_OK(hipSetDevice(e->device));
+    HIP_OK(hipDeviceSynchronize());
+    State &S = e->S;
+    hipStream_t st = e->stream;
+    SnapEvents E;
+    E.create();
+    read_counters(e);
+    const uint64_t n_ips = e->host_counters[0], used = e->host_counters[1], n_st = e->host_counters[2];
+    if (n_ips >= bjx_snap::kMaxIps) throw BjxError(BJX_ERR_CAPACITY, "bjx_state_export: 2^31 distinct IPs or more");
+    const uint32_t n_all = (uint32_t)e->names.size();
+
+    ExpAlloc tmp;
+    uint32_t *keep = tmp.get<uint32_t>(n_ips + 1), *nid = tmp.get<uint32_t>(n_ips + 1);
+    uint64_t *klen = tmp.get<uint64_t>(n_ips + 1), *noff = tmp.get<uint64_t>(n_ips + 1);
+    uint32_t *d_used = tmp.get<uint32_t>(n_all + 1), *d_remap = tmp.get<uint32_t>(n_all + 1);
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_export: no device memory for the scan buffers");
+    e->chk.ensure(8);
+    HIP_OK(hipEventRecord(E.ev[0], st));
+    HIP_OK(hipMemsetAsync(keep, 0, (n_ips + 1) * 4, st));
+    HIP_OK(hipMemsetAsync(d_used, 0, (n_all + 1) * 4, st));
+    HIP_OK(hipMemsetAsync(e->chk.p, 0, 16, st));
+    hipLaunchKernelGGL(k_exp_mark, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st, e->st_cap,
+                       S.st, min_start_ns, n_ips, keep, e->chk.p);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_exp_len, dim3(grid_for(n_ips + 1)), dim3(kBlock), 0, st, n_ips, keep, S.ip_len, klen);
+    HIP_OK(hipGetLastError());
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, keep, nid, (int)(n_ips + 1), st); });
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, klen, noff, (int)(n_ips + 1), st); });
+    HIP_OK(hipEventRecord(E.ev[1], st));
+    unsigned long long kept_st = 0;
+    uint32_t kept_ips32 = 0;
+    uint64_t kept_bytes = 0;
+    pin_get(e, &kept_st, e->chk.p, 8);
+    pin_get(e, &kept_ips32, nid + n_ips, 4);
+    pin_get(e, &kept_bytes, noff + n_ips, 8);
+    pin_sync(e);
+    const uint64_t kept_ips = kept_ips32;
+    if (kept_ips > n_ips || kept_bytes > used || kept_st > e->st_cap)
+      throw BjxError(BJX_ERR_DEVICE, "internal: export counts exceed the tables");
+    if (kept_st >= bjx_snap::kMaxStates) throw BjxError(BJX_ERR_CAPACITY, "bjx_state_export: 2^31 states or more");
+
+    // records, unsorted, with the engine's name ids; the names in use
+    uint64_t *keys = tmp.get<uint64_t>(kept_st), *keys2 = tmp.get<uint64_t>(kept_st);
+    uint32_t *idx = tmp.get<uint32_t>(kept_st), *idx2 = tmp.get<uint32_t>(kept_st);
+    int64_t *pay = tmp.get<int64_t>(2 * kept_st);
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_export: no device memory for the records");
+    HIP_OK(hipEventRecord(E.ev[2], st));
+    if (kept_st) {
+      hipLaunchKernelGGL(k_snap_compact, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st,
+                         e->st_cap, S.st, min_start_ns, n_ips, nid, n_all, d_used, e->chk.p + 1, (uint64_t)kept_st, keys, idx, pay);
+      HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipEventRecord(E.ev[3], st));
+    unsigned long long packed = 0;
+    std::vector<uint32_t> h_used(n_all + 1, 0);
+    pin_get(e, &packed, e->chk.p + 1, 8);
+    pin_sync(e);
+    HIP_OK(hipMemcpy(h_used.data(), d_used, (n_all + 1) * 4, hipMemcpyDeviceToHost));
+    if (packed != kept_st) throw BjxError(BJX_ERR_DEVICE, "internal: export passes disagree on the surviving states");
+
+    // canonical names: the used ones sorted bytewise; old id -> canonical index
+    std::vector<std::string> canon;
+    for (uint32_t k = 0; k < n_all; ++k)
+      if (h_used[k]) canon.push_back(e->names[k]);
+    std::sort(canon.begin(), canon.end());
+    std::vector<uint32_t> remap(n_all + 1, 0);
+    uint64_t names_bytes = 0;
+    for (auto &x : canon) names_bytes += x.size();
+    for (uint32_t k = 0; k < n_all; ++k)
+      if (h_used[k]) remap[k] = (uint32_t)(std::lower_bound(canon.begin(), canon.end(), e->names[k]) - canon.begin());
+    bjx_snap::Layout L;
+    const char *why = nullptr;
+    if (!bjx_snap::make_layout(canon.size(), names_bytes, kept_ips, kept_bytes, kept_st, &L, &why))
+      throw BjxError(BJX_ERR_CAPACITY, std::string("bjx_state_export: ") + why);
+    if (len) *len = L.total;
+    if (cap < L.total)
+      throw BjxError(BJX_ERR_CAPACITY, "bjx_state_export: the snapshot takes " + std::to_string(L.total) + " bytes, cap is " +
+                                           std::to_string(cap));
+
+    // the snapshot from ip_off on, built in device memory
+    const uint64_t body = L.total - L.o_ip_off;
+    uint8_t *d_body = tmp.get<uint8_t>(body + 16);
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_export: no device memory for the snapshot");
+    uint64_t *d_ipoff = reinterpret_cast<uint64_t *>(d_body);
+    uint8_t *d_ipb = d_body + (L.o_ips - L.o_ip_off);
+    uint64_t *d_recs = reinterpret_cast<uint64_t *>(d_body + (L.o_recs - L.o_ip_off));
+    HIP_OK(hipMemcpyAsync(d_remap, remap.data(), (n_all + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipEventRecord(E.ev[4], st));
+    HIP_OK(hipMemsetAsync(d_body, 0, L.o_recs - L.o_ip_off, st));  // the padding after the IP bytes
+    if (kept_st) {
+      hipLaunchKernelGGL(k_snap_remap, dim3(grid_for(kept_st)), dim3(kBlock), 0, st, (uint64_t)kept_st, keys, d_remap);
+      HIP_OK(hipGetLastError());
+      const int end_bit = 24 + std::max(1, bit_width(kept_ips));
+      cub_call(e, [&](void *t, size_t &b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, keys, keys2, idx, idx2, (int)kept_st, 0, end_bit, st);
+      });
+      hipLaunchKernelGGL(k_snap_gather, dim3(grid_for(kept_st)), dim3(kBlock), 0, st, (uint64_t)kept_st, keys2, idx2, pay, d_recs);
+      HIP_OK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_snap_ips, dim3(grid_for(n_ips + 1)), dim3(kBlock), 0, st, n_ips, keep, nid, noff, S.ip_off, S.ip_len,
+                       S.arena, used, kept_ips, kept_bytes, d_ipoff, d_ipb);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(E.ev[5], st));
+    HIP_OK(hipStreamSynchronize(st));
+
+    bjx_snap::write_header(out, L);
+    bjx_snap::write_names(out, L, canon);
+    snap_copy_out(e, out + L.o_ip_off, d_body, body);
+    if (stats) {
+      stats->ips = kept_ips; stats->states = kept_st; stats->names = canon.size(); stats->bytes = L.total;
+      stats->ips_skipped = n_ips - kept_ips;
+      stats->states_skipped = n_st - std::min<uint64_t>(n_st, kept_st);
+      stats->device_ms = E.ms(0, 1) + E.ms(2, 3) + E.ms(4, 5);
+    }
+    return BJX_OK;
+  } catch (const BjxError &x) {
+    e->last_error = x.what();
+    return x.code;
+  } catch (const std::bad_alloc &) {
+    e->last_error = "host out of memory";
+    return BJX_ERR_NOMEM;
+  }
+}
+
+// Import into an empty engine: the snapshot's tail is uploaded and checked on
+// the device, the IPs this part owns are scanned into dense ids and arena
+// offsets, and new tables are built from them and swapped in.  Nothing of the
+// engine changes before the swap, so every failure leaves it empty.
+extern "C" int bjx_state_import(bjx_engine *e, const uint8_t *snap, uint64_t len, uint32_t part, uint32_t n_parts,
+                                bjx_snapshot_stats *stats) {
+  if (!e) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  try {
+    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_import between bjx_match_batch and its bjx_finish_batch");
+    if (!snap) throw BjxError(BJX_ERR_ARG, "bjx_state_import: no snapshot");
+    if (n_parts < 1 || n_parts > kMaxParts || part >= n_parts)
+      throw BjxError(BJX_ERR_ARG, "bjx_state_import: part / n_parts out of range (n_parts 1..256, part < n_parts)");
+    HIP_OK(hipSetDevice(e->device));
+    HIP_OK(hipDeviceSynchronize());
+    State &S = e->S;
+    hipStream_t st = e->stream;
+    read_counters(e);
+    if (e->host_counters[0] || e->host_counters[2])
+      throw BjxError(BJX_ERR_ARG, "bjx_state_import: the engine holds state (import needs an empty engine)");
+    bjx_snap::Layout L;
+    std::vector<std::string> names;
+    if (const char *why = bjx_snap::validate_host(snap, len, &L, &names))
+      throw BjxError(BJX_ERR_ARG, std::string("bjx_state_import: ") + why);
+    const uint64_t n_ips = L.n_ips, n_states = L.n_states;
+    const uint32_t n_names = (uint32_t)L.n_names;
+    SnapEvents E;
+    E.create();
+
+    const uint64_t body = L.total - L.o_ip_off;
+    ExpAlloc tmp;
+    uint8_t *d_body = tmp.get<uint8_t>(body + 16);
+    uint32_t *keep = tmp.get<uint32_t>(n_ips + 1), *nid = tmp.get<uint32_t>(n_ips + 1);
+    uint64_t *klen = tmp.get<uint64_t>(n_ips + 1), *noff = tmp.get<uint64_t>(n_ips + 1), *hash = tmp.get<uint64_t>(n_ips + 1);
+    uint32_t *d_used = tmp.get<uint32_t>(n_names + 1), *d_remap = tmp.get<uint32_t>(n_names + 1), *d_err = tmp.get<uint32_t>(8);
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_import: no device memory for the snapshot");
+    const uint64_t *d_ipoff = reinterpret_cast<const uint64_t *>(d_body);
+    const uint8_t *d_ipb = d_body + (L.o_ips - L.o_ip_off);
+    const uint64_t *d_recs = reinterpret_cast<const uint64_t *>(d_body + (L.o_recs - L.o_ip_off));
+    snap_copy_in(e, d_body, snap + L.o_ip_off, body);
+
+    // the device checks: nothing else runs before they pass
+    HIP_OK(hipEventRecord(E.ev[0], st));
+    HIP_OK(hipMemsetAsync(d_err, 0, 32, st));
+    HIP_OK(hipMemsetAsync(d_used, 0, (n_names + 1) * 4, st));
+    hipLaunchKernelGGL(k_imp_check, dim3(grid_for(std::max(n_ips + 1, n_states))), dim3(kBlock), 0, st, n_ips, d_ipoff, L.ip_bytes,
+                       n_states, d_recs, n_names, d_used, d_err);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(E.ev[1], st));
+    uint32_t err[8] = {};
+    std::vector<uint32_t> h_used(n_names + 1, 0);
+    pin_get(e, err, d_err, 32);
+    pin_sync(e);
+    HIP_OK(hipMemcpy(h_used.data(), d_used, (n_names + 1) * 4, hipMemcpyDeviceToHost));
+    static const char *const kWhy[7] = {"", "ip_off: not monotone from 0", "ip_off: does not end at ip_bytes",
+                                        "records: ip index out of range", "records: name index out of range",
+                                        "records: not strictly ascending by (ip, name)", "records: an IP without a record"};
+    for (int c = 1; c < 7; ++c)
+      if (err[c]) throw BjxError(BJX_ERR_ARG, std::string("bjx_state_import: ") + kWhy[c]);
+    for (uint32_t k = 0; k < n_names; ++k)
+      if (!h_used[k]) throw BjxError(BJX_ERR_ARG, "bjx_state_import: names: a name no record uses");
+
+    // names into this engine's ids
+    std::vector<uint32_t> remap(n_names + 1, 0);
+    for (uint32_t k = 0; k < n_names; ++k) remap[k] = intern_name(e, names[k]);
+    HIP_OK(hipMemcpyAsync(d_remap, remap.data(), (n_names + 1) * 4, hipMemcpyHostToDevice, st));
+
+    // per IP: hash, owner filter; dense ids and arena offsets of the kept ones
+    e->chk.ensure(8);
+    HIP_OK(hipEventRecord(E.ev[2], st));
+    HIP_OK(hipMemsetAsync(e->chk.p, 0, 8, st));
+    hipLaunchKernelGGL(k_imp_ip, dim3(grid_for(n_ips + 1)), dim3(kBlock), 0, st, n_ips, d_ipoff, d_ipb, part, n_parts, keep, klen,
+                       hash);
+    HIP_OK(hipGetLastError());
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, keep, nid, (int)(n_ips + 1), st); });
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, klen, noff, (int)(n_ips + 1), st); });
+    if (n_states) {
+      hipLaunchKernelGGL(k_imp_count, dim3(grid_for(n_states)), dim3(kBlock), 0, st, n_states, d_recs, keep, e->chk.p);
+      HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipEventRecord(E.ev[3], st));
+    unsigned long long kept_st = 0;
+    uint32_t kept_ips32 = 0;
+    uint64_t kept_bytes = 0;
+    pin_get(e, &kept_st, e->chk.p, 8);
+    pin_get(e, &kept_ips32, nid + n_ips, 4);
+    pin_get(e, &kept_bytes, noff + n_ips, 8);
+    pin_sync(e);
+    const uint64_t kept_ips = kept_ips32;
+    if (kept_ips > n_ips || kept_bytes > L.ip_bytes || kept_st > n_states)
+      throw BjxError(BJX_ERR_DEVICE, "internal: import counts exceed the snapshot");
+
+    // the new tables: the growth rule on what this part keeps, never below the
+    // capacities the engine was created with; allocated before the old go
+    const uint64_t ip_cap = std::max(e->ip_cap0, next_pow2(kept_ips * 4 / 3 + 1024));
+    const uint64_t st_cap = std::max(e->st_cap0, next_pow2(kept_st * 4 / 3 + 1024));
+    const uint64_t arena_cap = std::max(e->arena_cap0, next_pow2(2 * kept_bytes + 4096));
+    ExpAlloc nw;
+    IpSlot *n_ip = nw.get<IpSlot>(ip_cap);
+    uint32_t *n_first = nw.get<uint32_t>(ip_cap);
+    uint64_t *n_off = nw.get<uint64_t>(ip_cap);
+    uint32_t *n_len = nw.get<uint32_t>(ip_cap);
+    uint32_t *n_ipst = nw.get<uint32_t>(ip_cap);
+    uint8_t *n_arena = nw.get<uint8_t>(arena_cap);
+    StSlot *n_stt = nw.get<StSlot>(st_cap);
+    if (nw.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_import: no device memory for the tables (the engine stays empty)");
+    // born: non-zero and below every later batch's epoch (run_batch counts up before it claims)
+    if (e->epoch == 0) e->epoch = 1;
+    const uint32_t born = e->epoch;
+    HIP_OK(hipEventRecord(E.ev[4], st));
+    HIP_OK(hipMemsetAsync(n_ip, 0, ip_cap * sizeof(IpSlot), st));
+    HIP_OK(hipMemsetAsync(n_first, 0xFF, ip_cap * 4, st));
+    HIP_OK(hipMemsetAsync(n_ipst, 0xFF, ip_cap * 4, st));
+    HIP_OK(hipMemsetAsync(n_stt, 0, st_cap * sizeof(StSlot), st));
+    if (n_ips) {
+      hipLaunchKernelGGL(k_imp_place, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, keep, nid, noff, hash, e->dbg_hash_mask,
+                         d_ipoff, d_ipb, born, kept_ips, n_arena, arena_cap, n_off, n_len, n_ip, ip_cap - 1);
+      HIP_OK(hipGetLastError());
+    }
+    if (n_states) {
+      hipLaunchKernelGGL(k_imp_st, dim3(grid_for(n_states)), dim3(kBlock), 0, st, n_states, d_recs, keep, nid, d_remap, n_stt,
+                         st_cap - 1);
+      HIP_OK(hipGetLastError());
+    }
+    if (n_ips) {
+      hipLaunchKernelGGL(k_imp_verify, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, keep, nid, hash, e->dbg_hash_mask,
+                         d_ipoff, d_ipb, kept_ips, n_ip, ip_cap - 1, n_off, n_len, n_arena, d_err);
+      HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipEventRecord(E.ev[5], st));
+    pin_get(e, err, d_err, 4);
+    pin_sync(e);
+    if (err[0]) throw BjxError(BJX_ERR_ARG, "bjx_state_import: ips: an IP appears twice in the snapshot");
+
+    // swap, as expiry does
+    nw.take();
+    for (void *p : {(void *)S.ip, (void *)S.ip_first, (void *)S.ip_off, (void *)S.ip_len, (void *)S.ip_st, (void *)S.arena,
+                    (void *)S.st})
+      (void)hipFree(p);
+    S.ip = n_ip; S.ip_first = n_first; S.ip_off = n_off; S.ip_len = n_len; S.ip_st = n_ipst; S.arena = n_arena; S.st = n_stt;
+    S.ip_mask = ip_cap - 1;
+    S.st_mask = st_cap - 1;
+    S.arena_cap = arena_cap;
+    S.ip_st_cap = ip_cap;
+    if (st_cap > (1ull << 32)) S.hot_name = kNone;
+    else if (e->st_cap > (1ull << 32)) e->bound_uid = 0;
+    e->ip_cap = ip_cap;
+    e->st_cap = st_cap;
+    e->sort2_hold = 0;
+    hipLaunchKernelGGL(k_exp_counters, dim3(1), dim3(64), 0, st, S.counters, kept_ips, kept_bytes, (uint64_t)kept_st);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(st));
+    e->host_counters[0] = kept_ips; e->host_counters[1] = kept_bytes; e->host_counters[2] = kept_st;
+    e->counters_fresh = false;
+    if (stats) {
+      stats->ips = kept_ips; stats->states = kept_st; stats->names = n_names; stats->bytes = len;
+      stats->ips_skipped = n_ips - kept_ips;
+      stats->states_skipped = n_states - kept_st;
+      stats->device_ms = E.ms(0, 1) + E.ms(2, 3) + E.ms(4, 5);
     }
     return BJX_OK;
   } catch (const BjxError &x) {

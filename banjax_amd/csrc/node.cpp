@@ -42,6 +42,7 @@
 
 #include "../../include/banjax_gpu.h"
 #include "../../include/banjax_gpu_debug.h"
+#include "snapshot.h"
 
 namespace {
 
@@ -834,6 +835,93 @@ extern "C" int bjx_node_state_expire(bjx_node *n, int64_t cutoff_ns, bjx_expire_
   }
   if (out) *out = t;
   return BJX_OK;
+}
+
+// the sum of the shards' bounds: each holds its own header and name table, the merged snapshot one of each
+extern "C" uint64_t bjx_node_state_export_bound(bjx_node *n) {
+  if (!n) return 0;
+  std::lock_guard<std::mutex> g(n->mu);
+  uint64_t t = 0;
+  for (auto &P : n->parts) {
+    const uint64_t b = bjx_state_export_bound(P.e);
+    if (!b) return 0;
+    t += b;
+  }
+  return t;
+}
+
+// every shard's export, then the host merge (snapshot.h): shards concatenated
+// engine-major, IP indices offset, names remapped to the sorted union
+extern "C" int bjx_node_state_export(bjx_node *n, int64_t min_start_ns, uint8_t *out, uint64_t cap, uint64_t *len,
+                                     bjx_snapshot_stats *stats) {
+  if (!n) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    if (len) *len = 0;
+    if (cap && !out) fail(BJX_ERR_ARG, "bjx_node_state_export: no output buffer");
+    const size_t N = n->parts.size();
+    std::vector<std::vector<uint8_t>> blob(N);
+    std::vector<std::pair<const uint8_t *, uint64_t>> shards(N);
+    bjx_snapshot_stats t{};
+    for (size_t k = 0; k < N; ++k) {
+      bjx_engine *e = n->parts[k].e;
+      blob[k].resize(bjx_state_export_bound(e));
+      uint64_t got = 0;
+      bjx_snapshot_stats s{};
+      const int rc = bjx_state_export(e, min_start_ns, blob[k].data(), blob[k].size(), &got, &s);
+      if (rc != BJX_OK) fail(rc, "engine " + std::to_string(k) + ": " + bjx_engine_last_error(e));
+      shards[k] = {blob[k].data(), got};
+      t.ips += s.ips; t.states += s.states; t.ips_skipped += s.ips_skipped; t.states_skipped += s.states_skipped;
+      if (s.device_ms > t.device_ms) t.device_ms = s.device_ms;
+    }
+    std::vector<uint8_t> merged;
+    bool capacity = false;
+    if (const char *why = bjx_snap::merge(shards, &merged, &capacity))
+      fail(capacity ? BJX_ERR_CAPACITY : BJX_ERR_DEVICE, std::string("bjx_node_state_export: merge: ") + why);
+    if (len) *len = merged.size();
+    if (cap < merged.size())
+      fail(BJX_ERR_CAPACITY, "bjx_node_state_export: the snapshot takes " + std::to_string(merged.size()) + " bytes, cap is " +
+                                 std::to_string(cap));
+    memcpy(out, merged.data(), merged.size());
+    if (stats) {
+      t.names = bjx_snap::rd64(merged.data() + 24);
+      t.bytes = merged.size();
+      *stats = t;
+    }
+    return BJX_OK;
+  });
+}
+
+// engine k takes part k of n; a failure clears the engines that had imported
+extern "C" int bjx_node_state_import(bjx_node *n, const uint8_t *snap, uint64_t len, bjx_snapshot_stats *stats) {
+  if (!n) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    const size_t N = n->parts.size();
+    bjx_snapshot_stats t{};
+    for (size_t k = 0; k < N; ++k) {
+      bjx_state_stats s{};
+      const int rc = bjx_state_stats_get(n->parts[k].e, &s);
+      if (rc != BJX_OK) fail(rc, "engine " + std::to_string(k) + ": " + bjx_engine_last_error(n->parts[k].e));
+      if (s.ips || s.states) fail(BJX_ERR_ARG, "bjx_node_state_import: the node holds state (import needs an empty node)");
+    }
+    for (size_t k = 0; k < N; ++k) {
+      bjx_engine *e = n->parts[k].e;
+      bjx_snapshot_stats s{};
+      const int rc = bjx_state_import(e, snap, len, (uint32_t)k, (uint32_t)N, &s);
+      if (rc != BJX_OK) {
+        const std::string msg = "engine " + std::to_string(k) + ": " + bjx_engine_last_error(e);
+        for (size_t j = 0; j < k; ++j) (void)bjx_state_clear(n->parts[j].e);  // they hold parts of the snapshot
+        fail(rc, msg);
+      }
+      t.ips += s.ips; t.states += s.states; t.names = s.names; t.bytes = s.bytes;
+      if (s.device_ms > t.device_ms) t.device_ms = s.device_ms;
+      if (k == 0) { t.ips_skipped = s.ips + s.ips_skipped; t.states_skipped = s.states + s.states_skipped; }
+    }
+    // what no engine took (none: every IP has one owner)
+    t.ips_skipped -= t.ips;
+    t.states_skipped -= t.states;
+    if (stats) *stats = t;
+    return BJX_OK;
+  });
 }
 
 extern "C" int bjx_node_state_clear(bjx_node *n) {

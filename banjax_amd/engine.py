@@ -8,6 +8,8 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 from . import _lib
 from .config import Config, Ruleset
 
+INT64_MIN = -(1 << 63)
+
 
 class BatchOutput:
     """Host view of one bjx_process_batch.  The arrays live in engine-owned
@@ -326,6 +328,41 @@ class Engine:
         _lib.lib().bjx_state_dump(self._h, buf, n)
         return buf.raw[:n].decode(errors="replace")
 
+    _snap = "bjx_state"
+
+    def state_export_bound(self) -> int:
+        """An upper bound on the size of state_export()'s blob (no pass over the tables)."""
+        return getattr(_lib.lib(), self._snap + "_export_bound")(self._h)
+
+    def state_export(self, min_start_ns: int = INT64_MIN, cap: Optional[int] = None) -> bytes:
+        """The rate-limit state as one snapshot blob (banjax_amd/snapshot.py has
+        the format): every state whose window started at or after min_start_ns.
+        The engine is unchanged.  cap: the buffer size to offer (default: the
+        library's bound); too small raises BJX_ERR_CAPACITY with the size
+        needed in the error's `needed`.  The call's bjx_snapshot_stats are left
+        in self.snapshot_stats."""
+        L = _lib.lib()
+        if cap is None:
+            cap = self.state_export_bound()
+        buf = (C.c_uint8 * max(cap, 1))()
+        n, st = C.c_uint64(0), _lib.SnapshotStats()
+        rc = getattr(L, self._snap + "_export")(self._h, min_start_ns, C.cast(buf, C.c_void_p), cap, C.byref(n), C.byref(st))
+        try:
+            self._check(rc, "state_export")
+        except _lib.BanjaxGpuError as x:
+            x.needed = n.value
+            raise
+        self.snapshot_stats = {k: getattr(st, k) for k, _ in _lib.SnapshotStats._fields_}
+        return bytes(memoryview(buf)[:n.value])
+
+    def state_import(self, blob: bytes, part: int = 0, n_parts: int = 1) -> dict:
+        """Restore a snapshot into this (empty) engine; with n_parts > 1 only the
+        IPs part `part` owns.  Returns the bjx_snapshot_stats fields."""
+        st = _lib.SnapshotStats()
+        blob = bytes(blob)
+        self._check(_lib.lib().bjx_state_import(self._h, blob, len(blob), part, n_parts, C.byref(st)), "state_import")
+        return {k: getattr(st, k) for k, _ in _lib.SnapshotStats._fields_}
+
     def close(self):
         h = getattr(self, "_h", None)
         if h and _lib._lib is not None:
@@ -448,6 +485,17 @@ class Node:
         buf = C.create_string_buffer(n + 1)
         _lib.lib().bjx_node_state_dump(self._h, buf, n)
         return buf.raw[:n].decode(errors="replace")
+
+    _snap = "bjx_node_state"
+    state_export_bound = Engine.state_export_bound
+    state_export = Engine.state_export  # the shards merged into one snapshot, IPs engine-major
+
+    def state_import(self, blob: bytes) -> dict:
+        """Restore a snapshot taken on any number of engines: engine k takes the IPs it owns."""
+        st = _lib.SnapshotStats()
+        blob = bytes(blob)
+        self._check(_lib.lib().bjx_node_state_import(self._h, blob, len(blob), C.byref(st)), "node_state_import")
+        return {k: getattr(st, k) for k, _ in _lib.SnapshotStats._fields_}
 
     def close(self):
         h = getattr(self, "_h", None)

@@ -529,6 +529,19 @@ class RegexRateLimiter:
         with self._mu:
             return self.engine.state_expire(expire_cutoff_ns(now_ns, self._snap.config))
 
+    def export_states(self, now_ns: Optional[int] = None) -> bytes:
+        """The rate-limit state as a snapshot blob (Engine.state_export) for the
+        host to write out on shutdown.  With now_ns only what expire_states(now_ns)
+        would keep is written (nothing is expired); without it, everything."""
+        with self._mu:
+            cutoff = _INT64_MIN if now_ns is None else expire_cutoff_ns(now_ns, self._snap.config)
+            return self.engine.state_export(cutoff)
+
+    def import_states(self, blob: bytes) -> dict:
+        """Restore a snapshot into the (empty) engine, before the first batch."""
+        with self._mu:
+            return self.engine.state_import(blob)
+
     def _ban_kw(self):
         if not self.device_bans:
             return {}

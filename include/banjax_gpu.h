@@ -304,6 +304,60 @@ typedef struct bjx_expire_stats {
   double device_ms;                                  /* device time of the pass (HIP events) */
 } bjx_expire_stats;
 int bjx_state_expire(bjx_engine *e, int64_t cutoff_ns, bjx_expire_stats *out);
+
+/* ---- Snapshot and restore of the rate-limit state (no counterpart in the
+   reference, whose few thousand states live in a Go map and are simply lost on
+   restart).  A snapshot carries the state out of the process -- across a
+   restart of the host, a library upgrade, a move to another GPU or to another
+   number of GPUs -- and back in before the first batch.
+
+   Format, version 1, little-endian (DESIGN.md §2 "Snapshot"):
+   a 64-byte header {magic[8] "BJXSTATE", u32 version = 1, u32 header_bytes =
+   64, u64 total_bytes, n_names, names_bytes, n_ips, ip_bytes, n_states}, then
+   u64 name_off[n_names + 1], the name bytes, u64 ip_off[n_ips + 1], the IP
+   bytes and n_states records {u32 ip, u32 name, i64 hits, i64 start}, each
+   section padded with zeros to 8 bytes.  The form is canonical: names sorted
+   bytewise, distinct, each used by a record; every IP with a record; records
+   strictly ascending by (ip, name).  The bytes depend on the logical state and
+   the IP order alone (not on slot layout, table sizes, name-id history or the
+   debug hash mask), so export(import(x)) == x.  Limits: n_names < 2^24,
+   n_ips < 2^31, n_states < 2^31 (past them export is BJX_ERR_CAPACITY).
+
+   bjx_state_export_bound: an upper bound on the snapshot's size from the
+   counters and the interned names, without a pass over the tables (0 on
+   error); allocate that much and call export once.
+
+   bjx_state_export writes every state with valid != 0 and interval_start_ns >=
+   min_start_ns and every IP that keeps at least one, IPs in first-seen order.
+   INT64_MIN exports everything; the trip-transparent cutoff of
+   bjx_state_expire exports exactly what an expiry would keep, without
+   expiring.  The engine is unchanged.  *len receives the exact size; cap too
+   small: BJX_ERR_CAPACITY with *len set, out unspecified.  Not legal between
+   bjx_match_batch and its bjx_finish_batch* (BJX_ERR_ARG), as expiry.
+
+   bjx_state_import is legal only on an engine that holds no state (ips == 0
+   and states == 0) and has no open batch (else BJX_ERR_ARG).  It takes the
+   IPs whose owner (hash_bytes(ip) >> 32) % n_parts == part -- the node's owner
+   function on the unmasked hash; pass 0, 1 for everything; n_parts 1..256.
+   Afterwards everything a caller can observe equals an engine that computed
+   that state itself: bjx_state_get / _len / _dump (IPs in snapshot order),
+   every later RuleResult (seen_ip, match_type, exceeded), trips and bans.
+   Rule names are interned into this engine, so import works before any
+   ruleset was bound and whatever ids the names had.  The tables are sized by
+   the growth rule on what is imported, never below the creation capacities.
+   A snapshot that fails validation: BJX_ERR_ARG, the message names the check;
+   a failed allocation: BJX_ERR_NOMEM; both leave the engine empty and usable.
+   stats and len may be NULL. */
+typedef struct bjx_snapshot_stats {
+  uint64_t ips, states, names, bytes;        /* what the snapshot holds / what was imported */
+  uint64_t ips_skipped, states_skipped;      /* export: below min_start_ns; import: owned by another part */
+  double device_ms;                          /* HIP events, copies excluded */
+} bjx_snapshot_stats;
+uint64_t bjx_state_export_bound(bjx_engine *e);
+int bjx_state_export(bjx_engine *e, int64_t min_start_ns, uint8_t *out, uint64_t cap, uint64_t *len,
+                     bjx_snapshot_stats *stats);
+int bjx_state_import(bjx_engine *e, const uint8_t *snap, uint64_t len, uint32_t part, uint32_t n_parts,
+                     bjx_snapshot_stats *stats);
 /* RegexRateLimitStates.String(): "ip:\n\trule:\n\t\t{hits start}\n" blocks, IPs in
    first-seen order.  Returns the full length (writes at most cap bytes). */
 size_t bjx_state_dump(bjx_engine *e, char *out, size_t cap);
@@ -460,6 +514,18 @@ int bjx_node_state_clear(bjx_node *n);
 /* bjx_state_expire on every shard with the same cutoff: counts and bytes
    summed, device_ms the slowest shard's.  out may be NULL. */
 int bjx_node_state_expire(bjx_node *n, int64_t cutoff_ns, bjx_expire_stats *out);
+/* Snapshot of the whole node: the shards' exports merged into one snapshot,
+   IPs engine-major (engine 0's in its first-seen order, then engine 1's, ...:
+   the order of bjx_node_state_dump); counts summed, device_ms the slowest
+   shard's.  Import: engine k imports with part = k, n_parts = size, so a
+   snapshot taken on any number of engines (or on one engine) restores into
+   any other number; a failure leaves every engine empty.  Both wait for the
+   node batch, as bjx_node_state_expire does.  Each engine uploads the whole
+   snapshot and keeps its part. */
+uint64_t bjx_node_state_export_bound(bjx_node *n);
+int bjx_node_state_export(bjx_node *n, int64_t min_start_ns, uint8_t *out, uint64_t cap, uint64_t *len,
+                          bjx_snapshot_stats *stats);
+int bjx_node_state_import(bjx_node *n, const uint8_t *snap, uint64_t len, bjx_snapshot_stats *stats);
 
 int bjx_abi_version(void);
 
