@@ -110,6 +110,7 @@ EXPORTS = [
     "bjx_node_state_clear", "bjx_node_exchange_kind", "bjx_state_expire", "bjx_node_state_expire",
     "bjx_state_export_bound", "bjx_state_export", "bjx_state_import",
     "bjx_node_state_export_bound", "bjx_node_state_export", "bjx_node_state_import",
+    "bjx_state_query", "bjx_node_state_query",
 ]
 
 
@@ -129,6 +130,28 @@ class SnapshotStats(C.Structure):
     """bjx_snapshot_stats: what one bjx_state_export / bjx_state_import moved."""
     _fields_ = [(k, C.c_uint64) for k in ("ips", "states", "names", "bytes", "ips_skipped", "states_skipped")] + \
                [("device_ms", C.c_double)]
+
+
+QUERY_BY_HITS, QUERY_BY_START, QUERY_MAX_ROWS = 0, 1, 65536
+
+
+class StateFilter(C.Structure):
+    """bjx_state_filter: which states a bjx_state_query counts and how it orders them (64 B)."""
+    _fields_ = [("ip", Str), ("name", Str), ("min_hits", C.c_int64), ("min_start_ns", C.c_int64),
+                ("max_start_ns", C.c_int64), ("order", C.c_uint32), ("limit", C.c_uint32)]
+
+
+class StateRow(C.Structure):
+    """bjx_state_row: one state of the answer; its IP and name lie in StateRows.bytes (40 B)."""
+    _fields_ = [("ip_off", C.c_uint64), ("name_off", C.c_uint64), ("ip_len", C.c_uint32), ("name_len", C.c_uint32),
+                ("hits", C.c_int64), ("start_ns", C.c_int64)]
+
+
+class StateRows(C.Structure):
+    """bjx_state_rows: counts and the first rows of a bjx_state_query (56 B)."""
+    _fields_ = [("n_matched", C.c_uint64), ("n_ips_matched", C.c_uint64), ("n_rows", C.c_uint64),
+                ("rows", C.POINTER(StateRow)), ("bytes", C.c_void_p), ("n_bytes", C.c_uint64),
+                ("device_ms", C.c_double)]
 
 
 _lib = None
@@ -281,6 +304,9 @@ def lib():
     L.bjx_state_import.argtypes = [vp, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(SnapshotStats)]
     L.bjx_node_state_import.restype = C.c_int
     L.bjx_node_state_import.argtypes = [vp, C.c_char_p, C.c_uint64, C.POINTER(SnapshotStats)]
+    for name in ("bjx_state_query", "bjx_node_state_query"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(StateRows)]
     _lib = L
     return L
 

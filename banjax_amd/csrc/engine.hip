@@ -43,6 +43,7 @@
 #include "regex_compiler.h"
 #include "bans.h"
 #include "snapshot.h"
+#include "state_query.h"
 
 using namespace bjx;
 
@@ -4680,6 +4681,226 @@ __global__ void k_snap_ips(uint64_t n_ips, const uint32_t *__restrict__ keep, co
   out_off[nid[i]] = d;
 }
 
+// state query (bjx_state_query; filter checks, sort key, name ranks, node
+// merge: state_query.h).  A state that passes the filter becomes a 16-byte
+// candidate {key_desc(primary), ip id << 24 | rank(name)}: ascending order of
+// that 128-bit key is the order of the rows.  k_qry_scan reads the state table
+// once (no ip filter), k_qry_ip probes one key per interned name (ip filter).
+// Selection is an MSB-first radix select, 8 bits a pass: k_qry_hist counts the
+// digits, the host picks the bucket the limit falls into, k_qry_filter moves
+// the buckets below it to the selected rows and that bucket to the next pass's
+// set.  What is left is sorted (two stable 64-bit sorts through an index) and
+// k_qry_rows / k_qry_bytes write the rows.  One atomic per block and pass
+// (block_alloc); every block runs the same number of passes.
+constexpr int kQryItems = 4;  // k_qry_scan: state slots per thread and pass
+struct QFilter {
+  int64_t min_hits, min_start, max_start;
+  uint32_t name;      // name id, kNone: every name
+  uint32_t by_start;  // primary key: 0 hits, 1 start
+};
+// (an id past n_ips or n_names cannot come from a finished batch: never followed, as st_survives)
+__device__ __forceinline__ bool q_pass(const StSlot &v, const QFilter &F, uint64_t n_ips, uint32_t n_names) {
+  const uint32_t name = (uint32_t)(v.key & 0xFFFFFFull);
+  return v.key != 0 && v.valid != 0 && (v.key >> 24) - 1 < n_ips && name < n_names && (F.name == kNone || name == F.name) &&
+         v.hits >= F.min_hits && v.start >= F.min_start && v.start <= F.max_start;
+}
+__device__ __forceinline__ ulonglong2 q_cand(const StSlot &v, const QFilter &F, const uint32_t *__restrict__ rank) {
+  return make_ulonglong2(bjx_query::key_desc(F.by_start ? v.start : v.hits),
+                         (((v.key >> 24) - 1) << 24) | rank[v.key & 0xFFFFFFull]);
+}
+// grid-stride; cnt[0] += passing states (one atomic per block), keep[ip id] = 1;
+// room != 0: the candidates appended at cnt[1]
+__global__ __launch_bounds__(kBlock) void k_qry_scan(uint64_t st_cap, const StSlot *__restrict__ st, QFilter F, uint64_t n_ips,
+                                                     uint32_t n_names, const uint32_t *__restrict__ rank,
+                                                     uint32_t *__restrict__ keep, unsigned long long *__restrict__ cnt,
+                                                     uint64_t room, ulonglong2 *__restrict__ cand) {
+  uint64_t n = 0, z = 0;
+  constexpr uint64_t kTile = (uint64_t)kBlock * kQryItems;  // slots per block and pass: one block_alloc for all of them
+  for (uint64_t base = (uint64_t)blockIdx.x * kTile; base < st_cap; base += (uint64_t)gridDim.x * kTile) {
+    ulonglong2 c[kQryItems];
+    uint32_t mask = 0;  // bit j: slot j of this thread passes (c[j] set)
+#pragma unroll
+    for (int j = 0; j < kQryItems; ++j) {
+      const uint64_t i = base + (uint64_t)j * kBlock + threadIdx.x;
+      c[j] = make_ulonglong2(0, 0);
+      if (i >= st_cap) continue;
+      const StSlot v = st[i];
+      if (!q_pass(v, F, n_ips, n_names)) continue;
+      keep[(v.key >> 24) - 1] = 1u;  // every writer stores the same value
+      if (room) c[j] = q_cand(v, F, rank);
+      mask |= 1u << j;
+    }
+    n += __popc(mask);
+    if (room) {
+      uint64_t k = block_alloc(&cnt[1], __popc(mask));
+#pragma unroll
+      for (int j = 0; j < kQryItems; ++j)
+        if ((mask >> j) & 1u) {
+          if (k < room) cand[k] = c[j];
+          ++k;
+        }
+    }
+  }
+  block_sum2(n, z);
+  if (threadIdx.x == 0 && n) atomicAdd(&cnt[0], (unsigned long long)n);
+}
+// Get(ip): the IP as k_state_get finds it (hash, probe chain, length and arena
+// bytes), then one lane per interned name id probes ((id + 1) << 24) | name
+__global__ __launch_bounds__(kBlock) void k_qry_ip(State S, uint64_t h, const uint8_t *__restrict__ ip, uint32_t len, QFilter F,
+                                                   uint64_t n_ips, uint32_t n_names, const uint32_t *__restrict__ rank,
+                                                   unsigned long long *__restrict__ cnt, uint64_t room,
+                                                   ulonglong2 *__restrict__ cand) {
+  __shared__ uint32_t s_id;
+  if (threadIdx.x == 0) {
+    uint32_t id = kNone;
+    for (uint64_t i = h & S.ip_mask;; i = (i + 1) & S.ip_mask) {
+      const uint64_t cur = S.ip[i].hash;
+      if (cur == 0) break;
+      if (cur == h) {
+        const uint32_t c = S.ip[i].id;
+        if (c < n_ips && S.ip_len[c] == len && bytes_eq(S.arena + S.ip_off[c], ip, len)) { id = c; break; }
+      }
+    }
+    s_id = id;
+  }
+  __syncthreads();
+  const uint32_t id = s_id;
+  uint64_t n = 0, z = 0;
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n_names; base += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t name = base + threadIdx.x;
+    StSlot v{};
+    bool ok = false;
+    if (id != kNone && name < n_names && (F.name == kNone || name == F.name)) {
+      const uint64_t key = ((uint64_t)(id + 1) << 24) | name;
+      for (uint64_t j = mix64(key) & S.st_mask;; j = (j + 1) & S.st_mask) {
+        const uint64_t k = S.st[j].key;
+        if (k == 0) break;
+        if (k == key) {
+          v = S.st[j];
+          ok = q_pass(v, F, n_ips, n_names);
+          break;
+        }
+      }
+    }
+    if (ok) ++n;
+    if (room) {
+      const uint64_t k = block_alloc(&cnt[1], ok ? 1 : 0);
+      if (ok && k < room) cand[k] = q_cand(v, F, rank);
+    }
+  }
+  block_sum2(n, z);
+  if (threadIdx.x == 0 && n) atomicAdd(&cnt[0], (unsigned long long)n);
+}
+__device__ __forceinline__ uint32_t q_digit(const ulonglong2 &c, uint32_t word, uint32_t shift) {
+  return (uint32_t)(((word ? c.y : c.x) >> shift) & 0xFFu);
+}
+// hist[d] += candidates whose digit (8 bits at `shift` of word 0 primary / 1
+// tie) is d.  A thread counts a run of equal digits before it touches LDS: the
+// high bytes of small hit counts are all one value.
+__global__ __launch_bounds__(kBlock) void k_qry_hist(const ulonglong2 *__restrict__ c, uint64_t n, uint32_t word, uint32_t shift,
+                                                     unsigned long long *__restrict__ hist) {
+  static_assert(kBlock == 256, "one histogram bin per thread");
+  __shared__ uint32_t s_h[256];
+  s_h[threadIdx.x] = 0;
+  __syncthreads();
+  uint32_t run_d = 0, run_n = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t d = q_digit(c[i], word, shift);
+    if (d != run_d && run_n) {
+      atomicAdd(&s_h[run_d], run_n);
+      run_n = 0;
+    }
+    run_d = d;
+    ++run_n;
+  }
+  if (run_n) atomicAdd(&s_h[run_d], run_n);
+  __syncthreads();
+  if (s_h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)s_h[threadIdx.x]);
+}
+// digit < b: selected (appended at ctr[0]); digit == b: the next pass's set (at ctr[1]); above: dropped
+__global__ __launch_bounds__(kBlock) void k_qry_filter(const ulonglong2 *__restrict__ c, uint64_t n, uint32_t word, uint32_t shift,
+                                                       uint32_t b, ulonglong2 *__restrict__ sel, uint64_t sel_room,
+                                                       ulonglong2 *__restrict__ nxt, uint64_t nxt_room,
+                                                       unsigned long long *__restrict__ ctr) {
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n; base += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t i = base + threadIdx.x;
+    ulonglong2 v = make_ulonglong2(0, 0);
+    uint32_t d = 256;
+    if (i < n) {
+      v = c[i];
+      d = q_digit(v, word, shift);
+    }
+    const uint64_t k0 = block_alloc(&ctr[0], d < b ? 1 : 0);
+    if (d < b && k0 < sel_room) sel[k0] = v;
+    const uint64_t k1 = block_alloc(&ctr[1], d == b ? 1 : 0);
+    if (d == b && k1 < nxt_room) nxt[k1] = v;
+  }
+}
+__global__ void k_qry_split(uint64_t n, const ulonglong2 *__restrict__ c, uint64_t *__restrict__ tie, uint32_t *__restrict__ idx) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  tie[i] = c[i].y;
+  idx[i] = (uint32_t)i;
+}
+__global__ void k_qry_prim(uint64_t n, const ulonglong2 *__restrict__ c, const uint32_t *__restrict__ idx,
+                           uint64_t *__restrict__ prim) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t s = idx[j];
+  prim[j] = s < n ? c[s].x : ~0ull;  // (a permutation of [0, n): always inside)
+}
+// row r = the r-th candidate in order: its state read back from the table,
+// the lengths of its IP and name; lens[r] = the bytes it takes ([0, n_rows]:
+// the last entry 0, the scan's total lands there)
+__global__ void k_qry_rows(uint64_t n_rows, uint64_t n_cand, const ulonglong2 *__restrict__ c, const uint32_t *__restrict__ idx,
+                           State S, uint64_t n_ips, uint32_t n_names, const uint32_t *__restrict__ by_rank,
+                           const uint64_t *__restrict__ name_off, bjx_state_row *__restrict__ rows,
+                           uint64_t *__restrict__ lens) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r > n_rows) return;
+  if (r == n_rows) { lens[r] = 0; return; }
+  bjx_state_row o{};
+  const uint32_t s = idx[r];
+  if (s < n_cand) {
+    const uint64_t tie = c[s].y, id = tie >> 24;
+    const uint32_t rk = (uint32_t)(tie & 0xFFFFFFull);
+    if (id < n_ips && rk < n_names) {
+      const uint64_t key = ((id + 1) << 24) | by_rank[rk];
+      for (uint64_t j = mix64(key) & S.st_mask;; j = (j + 1) & S.st_mask) {
+        const uint64_t k = S.st[j].key;
+        if (k == 0) break;
+        if (k == key) { o.hits = S.st[j].hits; o.start_ns = S.st[j].start; break; }
+      }
+      o.ip_len = S.ip_len[id];
+      o.name_len = (uint32_t)(name_off[rk + 1] - name_off[rk]);
+    }
+  }
+  rows[r] = o;
+  lens[r] = (uint64_t)o.ip_len + o.name_len;
+}
+// the rows' offsets and their bytes: IP, then name, at offs[r]
+__global__ void k_qry_bytes(uint64_t n_rows, uint64_t n_cand, const ulonglong2 *__restrict__ c, const uint32_t *__restrict__ idx,
+                            State S, uint64_t n_ips, uint64_t arena_used, const uint64_t *__restrict__ name_off,
+                            const uint8_t *__restrict__ name_bytes, const uint64_t *__restrict__ offs, uint64_t total,
+                            bjx_state_row *__restrict__ rows, uint8_t *__restrict__ out) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rows) return;
+  const uint32_t s = idx[r];
+  const uint32_t il = rows[r].ip_len, nl = rows[r].name_len;
+  const uint64_t d = offs[r];
+  rows[r].ip_off = d;
+  rows[r].name_off = d + il;
+  if (s >= n_cand || d + il + nl > total) return;  // (not from a finished batch)
+  const uint64_t tie = c[s].y, id = tie >> 24;
+  if (id >= n_ips) return;
+  const uint64_t so = S.ip_off[id];
+  if (so + il > arena_used) return;
+  for (uint32_t k = 0; k < il; ++k) out[d + k] = S.arena[so + k];
+  if (!nl) return;  // (nl != 0: k_qry_rows found the rank inside the table)
+  const uint64_t no = name_off[tie & 0xFFFFFFull];
+  for (uint32_t k = 0; k < nl; ++k) out[d + il + k] = name_bytes[no + k];
+}
+
 // snapshot import (bjx_state_import).  err[c] = 1 (plain stores of one value)
 // when check c fails: 1 ip_off not monotone from 0, 2 ip_off[n_ips] !=
 // ip_bytes, 3 record ip >= n_ips, 4 record name >= n_names, 5 records not
@@ -5579,6 +5800,8 @@ struct bjx_engine {
   HostBuf<bjx_rule_result> results;
   HostBuf<uint8_t> line_flags;
   HostBuf<uint8_t> snap_pin;  // bjx_state_export / bjx_state_import: two pinned chunks the blob moves through
+  HostBuf<bjx_state_row> qry_rows;  // bjx_state_query: the last answer (valid until the next query)
+  HostBuf<uint8_t> qry_bytes;
 };
 
 namespace {
@@ -7213,6 +7436,8 @@ extern "C" void bjx_engine_destroy(bjx_engine *e) {
   e->ban_ips.release(); e->ban_log.release(); e->ban_off.release(); e->ban_kind.release(); e->ban_ipb.release();
   e->ban_ipo.release();
   e->snap_pin.release();
+  e->qry_rows.release();
+  e->qry_bytes.release();
   e->l_ip16.release(); e->jline.release(); e->jkey.release(); e->jidx.release(); e->jidx2.release(); e->jrec.release(); e->jkey2.release(); e->l_cand.release(); e->l_ccnt.release(); e->l_cfirst.release();
   (void)hipEventDestroy(e->ev0); (void)hipEventDestroy(e->ev1); (void)hipEventDestroy(e->evm0); (void)hipEventDestroy(e->evm1);
   for (auto &x : e->evk) (void)hipEventDestroy(x);
@@ -9455,6 +9680,226 @@ extern "C" int bjx_state_import(bjx_engine *e, const uint8_t *snap, uint64_t len
       stats->states_skipped = n_states - kept_st;
       stats->device_ms = E.ms(0, 1) + E.ms(2, 3) + E.ms(4, 5);
     }
+    return BJX_OK;
+  } catch (const BjxError &x) {
+    e->last_error = x.what();
+    return x.code;
+  } catch (const std::bad_alloc &) {
+    e->last_error = "host out of memory";
+    return BJX_ERR_NOMEM;
+  }
+}
+
+// ---- query: bjx_state_query (filter checks, sort key, name ranks: state_query.h)
+namespace {
+// the radix select stops at this many candidates for `need` rows still
+// wanted: what is left is sorted, so the sort stays O(limit)
+inline uint64_t qry_small(uint64_t need) { return 2 * need + 256; }
+}  // namespace
+
+// Query: one pass over the state table (or one probe per interned name of one
+// IP) counts the passing states and appends them as 16-byte candidates; a
+// radix select narrows them to the wanted rows plus a remainder of O(limit),
+// which is sorted; the rows and their bytes are gathered on the device and
+// copied out.  The tables are only read.  The candidate buffer is sized by the
+// `states` counter (the most a scan can append).
+extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_state_rows *out) {
+  if (!e || !f || !out) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  try {
+    memset(out, 0, sizeof *out);
+    if (const char *why = bjx_query::check_filter(f)) throw BjxError(BJX_ERR_ARG, std::string("bjx_state_query: ") + why);
+    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_query between bjx_match_batch and its bjx_finish_batch");
+    HIP_OK(hipSetDevice(e->device));
+    HIP_OK(hipDeviceSynchronize());
+    State &S = e->S;
+    hipStream_t st = e->stream;
+    SnapEvents E;
+    E.create();
+    read_counters(e);
+    const uint64_t n_ips = e->host_counters[0], used = e->host_counters[1], n_st = e->host_counters[2];
+    const uint32_t n_names = (uint32_t)e->names.size();
+    e->qry_rows.clear();
+    e->qry_bytes.clear();
+    QFilter F{f->min_hits, f->min_start_ns, f->max_start_ns, kNone, f->order == BJX_QUERY_BY_START ? 1u : 0u};
+    if (f->name.ptr) {
+      auto it = e->name_ids.find(std::string(f->name.ptr, f->name.len));
+      if (it == e->name_ids.end()) return BJX_OK;  // never interned: no state can carry it
+      F.name = it->second;
+    }
+    if (bjx_query::empty_window(*f) || !n_ips || !n_st || !n_names) return BJX_OK;
+    if (n_ips >= bjx_snap::kMaxIps) throw BjxError(BJX_ERR_CAPACITY, "bjx_state_query: 2^31 distinct IPs or more");
+    const bool by_ip = f->ip.ptr != nullptr;
+    const uint64_t limit = f->limit;
+    const uint64_t room = limit ? (by_ip ? (uint64_t)n_names : n_st) : 0;
+    const uint64_t rows_max = std::min(limit, room);
+    const uint64_t fin_cap = rows_max ? rows_max + qry_small(rows_max) : 0;
+
+    // name ranks (tie word), rank -> id and the name bytes in rank order (the rows' names)
+    std::vector<uint32_t> rank, by_rank;
+    bjx_query::name_ranks(e->names, &rank, &by_rank);
+    std::vector<uint64_t> noff(n_names + 1, 0);
+    std::string nbytes;
+    for (uint32_t r = 0; r < n_names; ++r) {
+      noff[r] = nbytes.size();
+      nbytes += e->names[by_rank[r]];
+    }
+    noff[n_names] = nbytes.size();
+
+    // every buffer whose size is known now, before anything is launched
+    ExpAlloc tmp;
+    uint32_t *keep = by_ip ? nullptr : tmp.get<uint32_t>(n_ips + 1);
+    uint32_t *d_sum = tmp.get<uint32_t>(4);
+    uint32_t *d_rank = tmp.get<uint32_t>(n_names), *d_by_rank = tmp.get<uint32_t>(n_names);
+    uint64_t *d_noff = tmp.get<uint64_t>(n_names + 1);
+    uint8_t *d_nbytes = tmp.get<uint8_t>(nbytes.size() + 16);
+    unsigned long long *d_ctr = tmp.get<unsigned long long>(4 + 256);  // [0] matched [1] appended [2] selected [3] next set; the histogram
+    ulonglong2 *cand = tmp.get<ulonglong2>(room), *fin = tmp.get<ulonglong2>(fin_cap);
+    uint64_t *k0 = tmp.get<uint64_t>(fin_cap), *k1 = tmp.get<uint64_t>(fin_cap);
+    uint32_t *i0 = tmp.get<uint32_t>(fin_cap), *i1 = tmp.get<uint32_t>(fin_cap);
+    bjx_state_row *d_rows = tmp.get<bjx_state_row>(rows_max);
+    uint64_t *d_lens = tmp.get<uint64_t>(rows_max + 1), *d_offs = tmp.get<uint64_t>(rows_max + 1);
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_query: no device memory for the candidates");
+    HIP_OK(hipMemcpyAsync(d_rank, rank.data(), n_names * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_by_rank, by_rank.data(), n_names * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_noff, noff.data(), (n_names + 1) * 8, hipMemcpyHostToDevice, st));
+    if (!nbytes.empty()) HIP_OK(hipMemcpyAsync(d_nbytes, nbytes.data(), nbytes.size(), hipMemcpyHostToDevice, st));
+    uint64_t h = 0;
+    if (by_ip) {
+      e->q_ip.ensure(f->ip.len + 1);
+      if (f->ip.len) HIP_OK(hipMemcpyAsync(e->q_ip.p, f->ip.ptr, f->ip.len, hipMemcpyHostToDevice, st));
+      h = hash_bytes(reinterpret_cast<const uint8_t *>(f->ip.ptr), (uint32_t)f->ip.len);
+      if (e->dbg_hash_mask) h = (h & e->dbg_hash_mask) | 1;
+    }
+    HIP_OK(hipStreamSynchronize(st));  // the uploads read host vectors
+    double ms = 0;
+
+    // 1. the passing states: counts, keep[], candidates
+    HIP_OK(hipEventRecord(E.ev[0], st));
+    HIP_OK(hipMemsetAsync(d_ctr, 0, (4 + 256) * 8, st));
+    HIP_OK(hipMemsetAsync(d_sum, 0, 16, st));
+    if (by_ip) {
+      hipLaunchKernelGGL(k_qry_ip, dim3((unsigned)std::min<uint64_t>(grid_for(n_names), 1024)), dim3(kBlock), 0, st, S, h,
+                         e->q_ip.p, (uint32_t)f->ip.len, F, n_ips, n_names, d_rank, d_ctr, room, cand);
+      HIP_OK(hipGetLastError());
+    } else {
+      HIP_OK(hipMemsetAsync(keep, 0, (n_ips + 1) * 4, st));
+      hipLaunchKernelGGL(k_qry_scan, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st, e->st_cap,
+                         S.st, F, n_ips, n_names, d_rank, keep, d_ctr, room, cand);
+      HIP_OK(hipGetLastError());
+      cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceReduce::Sum(t, b, keep, d_sum, (int)n_ips, st); });
+    }
+    HIP_OK(hipEventRecord(E.ev[1], st));
+    unsigned long long got[2] = {0, 0};
+    uint32_t ips_matched = 0;
+    pin_get(e, got, d_ctr, 16);
+    pin_get(e, &ips_matched, d_sum, 4);
+    pin_sync(e);
+    ms += E.ms(0, 1);
+    const uint64_t matched = got[0];
+    if (matched > n_st || (room && got[1] != matched))
+      throw BjxError(BJX_ERR_DEVICE, "internal: query counts disagree with the tables");
+    out->n_matched = matched;
+    out->n_ips_matched = by_ip ? (matched ? 1 : 0) : ips_matched;
+    const uint64_t n_rows = std::min(limit, matched);
+    if (!n_rows) {
+      out->device_ms = ms;
+      return BJX_OK;
+    }
+
+    // 2. radix select, most significant byte first: through the primary word
+    // into the tie word while the bucket the limit falls into is still large
+    ulonglong2 *cur = cand, *spare = nullptr;
+    uint64_t n_cur = matched, n_sel = 0, spare_cap = 0;
+    for (int pass = 0; pass < 16 && n_cur > qry_small(n_rows - n_sel); ++pass) {
+      const uint32_t word = pass < 8 ? 0u : 1u, shift = 56u - 8u * (uint32_t)(pass & 7);
+      const uint64_t need = n_rows - n_sel;
+      const unsigned grid = (unsigned)std::min<uint64_t>(grid_for(n_cur), 4096);
+      HIP_OK(hipEventRecord(E.ev[0], st));
+      HIP_OK(hipMemsetAsync(d_ctr + 4, 0, 256 * 8, st));
+      hipLaunchKernelGGL(k_qry_hist, dim3(grid), dim3(kBlock), 0, st, cur, n_cur, word, shift, d_ctr + 4);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipEventRecord(E.ev[1], st));
+      unsigned long long hist[256];
+      pin_get(e, hist, d_ctr + 4, sizeof hist);
+      pin_sync(e);
+      ms += E.ms(0, 1);
+      uint64_t below = 0;
+      uint32_t b = 0;
+      for (; b < 256 && below + hist[b] < need; ++b) below += hist[b];
+      if (b == 256) throw BjxError(BJX_ERR_DEVICE, "internal: query histogram does not add up");
+      const uint64_t in_b = hist[b];
+      if (in_b == n_cur) continue;  // every candidate has this digit: nothing to move
+      ulonglong2 *nxt;
+      if (cur == cand) {
+        if (!spare) {
+          spare = tmp.get<ulonglong2>(in_b);
+          spare_cap = in_b;
+          if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_query: no device memory for the selection");
+        }
+        nxt = spare;
+      } else {
+        nxt = cand;
+      }
+      const uint64_t nxt_cap = nxt == cand ? room : spare_cap;
+      if (in_b > nxt_cap || n_sel + below > fin_cap) throw BjxError(BJX_ERR_DEVICE, "internal: query selection exceeds its buffers");
+      HIP_OK(hipEventRecord(E.ev[0], st));
+      HIP_OK(hipMemsetAsync(d_ctr + 3, 0, 8, st));
+      hipLaunchKernelGGL(k_qry_filter, dim3(grid), dim3(kBlock), 0, st, cur, n_cur, word, shift, b, fin, fin_cap, nxt, nxt_cap,
+                         d_ctr + 2);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipEventRecord(E.ev[1], st));
+      unsigned long long moved[2] = {0, 0};
+      pin_get(e, moved, d_ctr + 2, 16);
+      pin_sync(e);
+      ms += E.ms(0, 1);
+      if (moved[0] != n_sel + below || moved[1] != in_b)
+        throw BjxError(BJX_ERR_DEVICE, "internal: query selection disagrees with its histogram");
+      n_sel += below;
+      n_cur = in_b;
+      cur = nxt;
+    }
+    const uint64_t m = n_sel + n_cur;
+    if (m > fin_cap || m < n_rows) throw BjxError(BJX_ERR_DEVICE, "internal: query selection did not converge");
+
+    // 3. sort the selected and the remainder by (primary, tie): two stable
+    // sorts through an index, the tie word first; gather the rows
+    HIP_OK(hipEventRecord(E.ev[0], st));
+    HIP_OK(hipMemcpyAsync(fin + n_sel, cur, n_cur * sizeof(ulonglong2), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_qry_split, dim3(grid_for(m)), dim3(kBlock), 0, st, m, fin, k0, i0);
+    HIP_OK(hipGetLastError());
+    const int tie_bits = std::min(64, 24 + std::max(1, bit_width(n_ips)));
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0, k1, i0, i1, (int)m, 0, tie_bits, st); });
+    hipLaunchKernelGGL(k_qry_prim, dim3(grid_for(m)), dim3(kBlock), 0, st, m, fin, i1, k0);
+    HIP_OK(hipGetLastError());
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0, k1, i1, i0, (int)m, 0, 64, st); });
+    hipLaunchKernelGGL(k_qry_rows, dim3(grid_for(n_rows + 1)), dim3(kBlock), 0, st, n_rows, m, fin, i0, S, n_ips, n_names, d_by_rank,
+                       d_noff, d_rows, d_lens);
+    HIP_OK(hipGetLastError());
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, d_lens, d_offs, (int)(n_rows + 1), st); });
+    HIP_OK(hipEventRecord(E.ev[1], st));
+    uint64_t total = 0;
+    pin_get(e, &total, d_offs + n_rows, 8);
+    pin_sync(e);
+    ms += E.ms(0, 1);
+    uint8_t *d_bytes = tmp.get<uint8_t>(total + 16);
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_query: no device memory for the rows' bytes");
+    HIP_OK(hipEventRecord(E.ev[0], st));
+    hipLaunchKernelGGL(k_qry_bytes, dim3(grid_for(n_rows)), dim3(kBlock), 0, st, n_rows, m, fin, i0, S, n_ips, used, d_noff, d_nbytes,
+                       d_offs, total, d_rows, d_bytes);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(E.ev[1], st));
+    e->qry_rows.resize(n_rows);
+    e->qry_bytes.resize(total + 1);
+    HIP_OK(hipMemcpyAsync(e->qry_rows.data(), d_rows, n_rows * sizeof(bjx_state_row), hipMemcpyDeviceToHost, st));
+    if (total) HIP_OK(hipMemcpyAsync(e->qry_bytes.data(), d_bytes, total, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    ms += E.ms(0, 1);
+    out->n_rows = n_rows;
+    out->rows = e->qry_rows.data();
+    out->bytes = e->qry_bytes.data();
+    out->n_bytes = total;
+    out->device_ms = ms;
     return BJX_OK;
   } catch (const BjxError &x) {
     e->last_error = x.what();

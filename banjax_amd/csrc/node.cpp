@@ -42,7 +42,9 @@
 
 #include "../../include/banjax_gpu.h"
 #include "../../include/banjax_gpu_debug.h"
+#include "bjx_common.h"
 #include "snapshot.h"
+#include "state_query.h"
 
 namespace {
 
@@ -118,6 +120,9 @@ struct bjx_node {
   std::vector<char> log;
   std::vector<uint64_t> log_off;
   std::vector<uint8_t> log_kind;
+  // the last bjx_node_state_query's merged answer
+  std::vector<bjx_state_row> q_rows;
+  std::vector<uint8_t> q_bytes;
 };
 
 namespace {
@@ -920,6 +925,32 @@ extern "C" int bjx_node_state_import(bjx_node *n, const uint8_t *snap, uint64_t 
     t.ips_skipped -= t.ips;
     t.states_skipped -= t.states;
     if (stats) *stats = t;
+    return BJX_OK;
+  });
+}
+
+// every shard's answer to the same filter and limit, merged on the host
+// (state_query.h); with an ip filter the owning engine's answer alone
+extern "C" int bjx_node_state_query(bjx_node *n, const bjx_state_filter *f, bjx_state_rows *out) {
+  if (!n || !f || !out) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    memset(out, 0, sizeof *out);
+    if (const char *why = bjx_query::check_filter(f)) fail(BJX_ERR_ARG, std::string("bjx_node_state_query: ") + why);
+    const size_t N = n->parts.size();
+    size_t first = 0, last = N;
+    if (f->ip.ptr) {
+      first = (size_t)((bjx::hash_bytes(reinterpret_cast<const uint8_t *>(f->ip.ptr), (uint32_t)f->ip.len) >> 32) % N);
+      last = first + 1;
+    }
+    std::vector<bjx_state_rows> ans;
+    for (size_t k = first; k < last; ++k) {
+      bjx_engine *e = n->parts[k].e;
+      bjx_state_rows a{};
+      const int rc = bjx_state_query(e, f, &a);
+      if (rc != BJX_OK) fail(rc, "engine " + std::to_string(k) + ": " + bjx_engine_last_error(e));
+      ans.push_back(a);
+    }
+    bjx_query::merge(ans, f->order, f->limit, out, &n->q_rows, &n->q_bytes);
     return BJX_OK;
   });
 }

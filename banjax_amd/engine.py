@@ -9,6 +9,7 @@ from . import _lib
 from .config import Config, Ruleset
 
 INT64_MIN = -(1 << 63)
+INT64_MAX = (1 << 63) - 1
 
 
 class BatchOutput:
@@ -363,6 +364,31 @@ class Engine:
         self._check(_lib.lib().bjx_state_import(self._h, blob, len(blob), part, n_parts, C.byref(st)), "state_import")
         return {k: getattr(st, k) for k, _ in _lib.SnapshotStats._fields_}
 
+    _query = "bjx_state_query"
+
+    def state_query(self, ip=None, name=None, min_hits: int = INT64_MIN, min_start_ns: int = INT64_MIN,
+                    max_start_ns: int = INT64_MAX, order: int = _lib.QUERY_BY_HITS, limit: int = 100) -> dict:
+        """Counts and the first `limit` states that pass the filter
+        (bjx_state_query; banjax_amd/state_query.py documents the order and is
+        its model).  ip / name None: every IP / rule name; b"" is a value.
+        order: _lib.QUERY_BY_HITS or _lib.QUERY_BY_START (or "hits" / "start").
+        limit 0: the counts only.  Returns {"n_matched", "n_ips_matched",
+        "rows": [(ip, name, hits, start_ns)] (bytes, bytes, int, int),
+        "device_ms"}.  The engine is unchanged."""
+        order = {"hits": _lib.QUERY_BY_HITS, "start": _lib.QUERY_BY_START}.get(order, order)
+        ipb = None if ip is None else _lib.b(ip)
+        nb = None if name is None else _lib.b(name)
+        f = _lib.StateFilter(_lib.Str(ipb, len(ipb or b"")), _lib.Str(nb, len(nb or b"")), min_hits, min_start_ns,
+                             max_start_ns, order, limit)
+        out = _lib.StateRows()
+        self._check(getattr(_lib.lib(), self._query)(self._h, C.byref(f), C.byref(out)), "state_query")
+        blob = C.string_at(out.bytes, out.n_bytes) if out.n_bytes else b""
+        rows = []
+        for k in range(out.n_rows):
+            r = out.rows[k]
+            rows.append((blob[r.ip_off:r.ip_off + r.ip_len], blob[r.name_off:r.name_off + r.name_len], r.hits, r.start_ns))
+        return {"n_matched": out.n_matched, "n_ips_matched": out.n_ips_matched, "rows": rows, "device_ms": out.device_ms}
+
     def close(self):
         h = getattr(self, "_h", None)
         if h and _lib._lib is not None:
@@ -489,6 +515,9 @@ class Node:
     _snap = "bjx_node_state"
     state_export_bound = Engine.state_export_bound
     state_export = Engine.state_export  # the shards merged into one snapshot, IPs engine-major
+
+    _query = "bjx_node_state_query"
+    state_query = Engine.state_query  # every shard's answer merged, IPs engine-major; an ip filter asks its owner only
 
     def state_import(self, blob: bytes) -> dict:
         """Restore a snapshot taken on any number of engines: engine k takes the IPs it owns."""

@@ -437,6 +437,20 @@ class RegexRateLimitStates:
                 out[name] = st
         return out if out else None
 
+    def get_all(self, ip: str) -> Optional[Dict[str, tuple]]:
+        """The reference's whole-map Get(ip) (rate_limit.go:81-96) in one call
+        (Engine.state_query with an ip filter): every rule state the IP holds,
+        also under a name that a reload removed from the config, which get()
+        above does not ask for.  {rule name: (NumHits, IntervalStartTime ns)},
+        or None."""
+        out, limit = {}, 65536
+        ans = self._e.state_query(ip=ip, limit=limit)
+        if ans["n_matched"] > limit:
+            raise RuntimeError("Get(%r): %d states, more than one query returns" % (ip, ans["n_matched"]))
+        for _, name, hits, start in ans["rows"]:
+            out[name.decode(errors="replace")] = (hits, start)
+        return out if out else None
+
     def __len__(self):
         return self._e.state_len()
 

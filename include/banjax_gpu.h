@@ -290,6 +290,9 @@ int bjx_state_clear(bjx_engine *e);
    such states: the expiry is trip-transparent.  Any other cutoff is allowed
    and simply means "those states are forgotten"; INT64_MAX equals
    bjx_state_clear in everything a caller can observe.
+   Preview: a counts-only bjx_state_query with max_start_ns = cutoff_ns - 1
+   reports as n_matched the states_dropped an expiry at cutoff_ns would, and
+   drops nothing.
 
    Takes the engine lock like the other bjx_state_* calls.  Not legal between
    bjx_match_batch and the bjx_finish_batch* that closes it (BJX_ERR_ARG; the
@@ -358,6 +361,69 @@ int bjx_state_export(bjx_engine *e, int64_t min_start_ns, uint8_t *out, uint64_t
                      bjx_snapshot_stats *stats);
 int bjx_state_import(bjx_engine *e, const uint8_t *snap, uint64_t len, uint32_t part, uint32_t n_parts,
                      bjx_snapshot_stats *stats);
+/* ---- Query: top-K, counts and Get(ip) over the state where it lives.
+   bjx_state_dump (RegexRateLimitStates.String, the /rate_limit_states route,
+   http_server.go:193-198) is text of every state and bjx_state_get answers one
+   (ip, name); this call answers "which IPs are closest to tripping rule X",
+   "how many states does rule X hold", "what would an expiry at this cutoff
+   drop" and the reference's whole-map Get(ip) (rate_limit.go:81-96) in one
+   pass, and a small answer comes back.
+
+   Which states count: those with valid != 0 -- exactly what bjx_state_export
+   writes -- that pass all five conditions of the filter.  n_matched counts
+   them, n_ips_matched the distinct IPs among them.
+
+   Order: total, and a function of the logical state alone.  Primary key
+   descending (hits for BJX_QUERY_BY_HITS, interval_start_ns for
+   BJX_QUERY_BY_START), then IP in first-seen order ascending (the order of
+   bjx_state_dump), then rule name bytewise ascending.  Slot layout, table
+   sizes, name-id history and the debug hash mask do not show.  The rows are
+   the first min(limit, n_matched) states in that order; limit 0 asks for the
+   counts only.
+
+   Not errors: a name the engine never interned or an IP it does not hold
+   (zero rows, zero counts); min_start_ns > max_start_ns (zero rows).
+   BJX_ERR_ARG: limit > BJX_QUERY_MAX_ROWS, an unknown order, a NULL f, out or
+   handle, a call between bjx_match_batch and its bjx_finish_batch* (the node
+   call waits for the node batch instead, as expiry and export do).  A failed
+   allocation: BJX_ERR_NOMEM.  The engine is unchanged in every case.  Takes
+   the engine lock like the other bjx_state_* calls.  rows and bytes are
+   engine-owned (node-owned for the node call) and stay valid until the next
+   query on that handle.
+
+   With an ip filter no table is scanned: the IP is found as bjx_state_get
+   finds it and one probe per interned name follows, so Get(ip) costs the
+   number of names the engine has ever seen -- and returns states kept under a
+   name a reload removed, as the reference's Get does.
+
+   Expiry preview: a counts-only query with max_start_ns = cutoff - 1 has
+   n_matched equal to the states_dropped bjx_state_expire(cutoff) would report
+   (cutoff > INT64_MIN; at INT64_MIN an expiry drops nothing). */
+enum bjx_query_order { BJX_QUERY_BY_HITS = 0, BJX_QUERY_BY_START = 1 };
+#define BJX_QUERY_MAX_ROWS 65536
+typedef struct bjx_state_filter {   /* 64 B */
+  bjx_str ip;            /* ptr NULL: every IP; else exactly these bytes (len 0 is a value): Get(ip) */
+  bjx_str name;          /* ptr NULL: every rule name; else exactly this name (len 0 is a value) */
+  int64_t min_hits;      /* hits >= min_hits        (INT64_MIN: all) */
+  int64_t min_start_ns;  /* interval_start_ns >= .. (INT64_MIN: all) */
+  int64_t max_start_ns;  /* interval_start_ns <= .. (INT64_MAX: all) */
+  uint32_t order;        /* enum bjx_query_order */
+  uint32_t limit;        /* rows wanted, 0..BJX_QUERY_MAX_ROWS; 0: counts only */
+} bjx_state_filter;
+typedef struct bjx_state_row {      /* 40 B */
+  uint64_t ip_off, name_off;        /* into bjx_state_rows.bytes */
+  uint32_t ip_len, name_len;
+  int64_t hits, start_ns;
+} bjx_state_row;
+typedef struct bjx_state_rows {     /* 56 B */
+  uint64_t n_matched;      /* states that pass the filter */
+  uint64_t n_ips_matched;  /* distinct IPs among them */
+  uint64_t n_rows;         /* min(limit, n_matched) */
+  const bjx_state_row *rows;
+  const uint8_t *bytes; uint64_t n_bytes;
+  double device_ms;        /* HIP events, copies excluded */
+} bjx_state_rows;
+int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_state_rows *out);
 /* RegexRateLimitStates.String(): "ip:\n\trule:\n\t\t{hits start}\n" blocks, IPs in
    first-seen order.  Returns the full length (writes at most cap bytes). */
 size_t bjx_state_dump(bjx_engine *e, char *out, size_t cap);
@@ -526,6 +592,15 @@ uint64_t bjx_node_state_export_bound(bjx_node *n);
 int bjx_node_state_export(bjx_node *n, int64_t min_start_ns, uint8_t *out, uint64_t cap, uint64_t *len,
                           bjx_snapshot_stats *stats);
 int bjx_node_state_import(bjx_node *n, const uint8_t *snap, uint64_t len, bjx_snapshot_stats *stats);
+/* bjx_state_query over the node.  Every shard answers the same filter and
+   limit and the host merges the answers: an IP lives on one engine and the
+   global first-seen order is the engine-major order of bjx_node_state_dump, so
+   the global first `limit` states are among the shards' first `limit` each.
+   Counts are summed, device_ms is the slowest shard's.  With an ip filter only
+   the owning engine is asked.  Waits for the node batch, as
+   bjx_node_state_expire does; rows and bytes are node-owned until the next
+   query on the node. */
+int bjx_node_state_query(bjx_node *n, const bjx_state_filter *f, bjx_state_rows *out);
 
 int bjx_abi_version(void);
 
