@@ -228,6 +228,8 @@ def lib():
     L.bjx_debug_rule_lead.argtypes = [vp, sz]
     L.bjx_debug_rule_literal.restype = sz
     L.bjx_debug_rule_literal.argtypes = [vp, sz, C.c_char_p, sz]
+    L.bjx_debug_ruleset_literals.restype = sz
+    L.bjx_debug_ruleset_literals.argtypes = [vp]
     L.bjx_debug_phase_ms.restype = sz
     L.bjx_debug_phase_ms.argtypes = [vp, C.POINTER(C.c_double), sz]
     L.bjx_debug_kernel_ms.restype = sz

@@ -663,4 +663,77 @@ BJX_HD bool is_v4_mapped(const uint8_t a[16]) {
   return a[10] == 0xFF && a[11] == 0xFF;
 }
 
+// ------------------------------------------------------------- literal-hit slots
+//
+// What a DFA job of a literal rule may conclude from a line's scan hits
+// (engine_types.h CandMeta; k_lines2's l2_job_rec and k_dfa_legacy's
+// lead_start / eq_certain share this; tests/cpu/hit_slots.cpp checks it over
+// every choice and order of the hits that got slots).  A slot word is
+// (literal start << 24) | kSlotVerified | literal id; the first kSlots hits to
+// arrive keep their word, in arrival order.  Every later one is folded into
+// the summary: bit (id & 31) of `bits`, bit 32 + (id & 31) as well when it is
+// verified and at least kSlotCertainGap bytes into the line, and first_inv =
+// max of ~(position >> 3).  `mine(word)`: the hit's literal is the rule's own.
+constexpr uint32_t kSlots = 4;
+constexpr uint64_t kSlotVerified = 1u << 23;
+constexpr uint32_t kSlotCertainGap = 256;
+
+// Offset in rest (rest = [rs, rs + rl)) where the job of a lead rule may start,
+// from the lowest candidate f of its literals (~0: none, no match: rl).  A
+// candidate before rest still bounds the first one in rest from below (0).
+// back: the bounded piece that may precede the literal.
+BJX_HD uint32_t lead_bound(uint64_t f, uint64_t rs, uint32_t rl, uint32_t back) {
+  if (f == ~0ull) return rl;
+  const uint64_t d = f <= rs ? 0ull : f - rs;
+  const uint32_t o = d < (uint64_t)rl ? (uint32_t)d : rl;
+  return o > back ? o - back : 0u;
+}
+
+// lead_bound from the slots: without overflow the lowest own hit at or past
+// rs; with overflow the lowest hit of any literal (a summarised hit may be the
+// own one), and 0 when a summarised hit may lie before rest.
+template <class Mine>
+BJX_HD uint32_t slot_lead_start(const uint64_t (&cv)[kSlots], uint32_t cnt, uint32_t first_inv, uint64_t rs, uint32_t rl,
+                                uint32_t back, Mine mine) {
+  const bool ovf = cnt > kSlots;
+  const uint32_t ns = cnt < kSlots ? cnt : kSlots;
+  uint64_t f = ~0ull;
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#pragma unroll
+#endif
+  for (uint32_t c = 0; c < kSlots; ++c) {
+    if (c >= ns) break;
+    const uint64_t v = cv[c];
+    const uint64_t q = v >> 24;
+    if (q < rs || q >= f) continue;
+    if (ovf || mine(v)) f = q;
+  }
+  if (ovf) {
+    const uint64_t mf = first_inv ? (uint64_t)(~first_inv) << 3 : ~0ull;
+    if (mf < rs) return 0u;
+    f = mf < f ? mf : f;
+  }
+  return lead_bound(f, rs, rl, back);
+}
+
+// An equivalent rule's literal occurs in rest for certain: a verified own
+// slot hit at or past rs, or, past the slots, the verified-and-far bit of one
+// of its literals (need: their bits (id & 31)) while a bit names one literal
+// (lits_small) and the header is no longer than kSlotCertainGap (so a far hit
+// lies in rest).
+template <class Mine>
+BJX_HD bool slot_certain(const uint64_t (&cv)[kSlots], uint32_t cnt, uint64_t bits, uint32_t need, bool lits_small,
+                         uint32_t rest_off, uint64_t rs, Mine mine) {
+  const uint32_t ns = cnt < kSlots ? cnt : kSlots;
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#pragma unroll
+#endif
+  for (uint32_t c = 0; c < kSlots; ++c) {
+    if (c >= ns) break;
+    const uint64_t v = cv[c];
+    if ((v & kSlotVerified) && (v >> 24) >= rs && mine(v)) return true;
+  }
+  return cnt > kSlots && lits_small && rest_off <= kSlotCertainGap && ((uint32_t)(bits >> 32) & need) != 0;
+}
+
 }  // namespace bjx

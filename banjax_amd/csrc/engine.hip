@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <set>
 #include <tuple>
 #include <memory>
 #include <mutex>
@@ -1870,8 +1871,16 @@ __global__ __launch_bounds__(kScanWaves * 64) __attribute__((amdgpu_waves_per_eu
       }
     }
     if (lane == 0 && head) ls[0] = 0;
-    const bool last_in_halo = n_st && !last_nl && hfirst != kNone;
-    const bool last_long = n_st && !last_nl && hfirst == kNone;
+    // a line that starts on the tile's first byte and has no '\n' in the tile
+    // is long even when it ends in the halo: the next tile sees no '\n' here
+    // and takes the line for one begun earlier (its open_long), so it records
+    // the halo part's hits itself, through the atomics.  Decided from LDS here
+    // as well, those hits were recorded twice and this tile's plain store of
+    // the hit count raced with the next tile's atomicAdd: a slot could end up
+    // holding a later hit in place of an earlier one, which was then lost.
+    const bool whole = head && tot == 0;
+    const bool last_in_halo = n_st && !last_nl && hfirst != kNone && !whole;
+    const bool last_long = n_st && !last_nl && (hfirst == kNone || whole);
     if (lane == 0 && last_in_halo && n_st - 1 < kLineCap) le[n_st - 1] = (uint16_t)hfirst;
     wave_sync();
     if (!B.any_prefilter || (A.debug_skip & 1)) continue;
@@ -2370,31 +2379,17 @@ __device__ __forceinline__ uint32_t lead_start(const Bind &B, const Lines &L, ui
       const uint64_t q = L.cand_first[j * kCandFirstLits + B.rule_lits[lo + k]];
       f = q < f ? q : f;
     }
-    if (f == ~0ull) return rl;  // none of its literals occurs: no match
-    // a first candidate in the header still bounds the first one in rest from below
-    const uint32_t o = f <= rs ? 0u : (uint32_t)min<uint64_t>(f - rs, rl);
-    return o > back ? o - back : 0u;
+    return bjx::lead_bound(f, rs, rl, back);
   }
   const CandMeta cm = L.cand_meta[j];
-  const bool ovf = cm.cnt > (uint32_t)kCandSlots;
-  uint64_t f = ~0ull;
-  const uint32_t ns = min(cm.cnt, (uint32_t)kCandSlots);
-  for (uint32_t c = 0; c < ns; ++c) {
-    const uint64_t v = L.cand[j * kCandSlots + c];
-    const uint64_t q = v >> 24;
-    if (q < rs || q >= f) continue;
-    bool mine = ovf;
-    for (uint32_t k = 0; k < ln && !mine; ++k) mine = B.rule_lits[lo + k] == (uint32_t)(v & 0x7FFFFF);
-    if (mine) f = q;
-  }
-  if (ovf) {
-    const uint64_t mf = cm.first_inv ? (uint64_t)(~cm.first_inv) << 3 : ~0ull;
-    if (mf < rs) return 0;
-    f = mf < f ? mf : f;
-  }
-  if (f == ~0ull) return rl;
-  const uint32_t o = (uint32_t)min<uint64_t>(f - rs, rl);
-  return o > back ? o - back : 0u;
+  uint64_t cv[kCandSlots];
+  for (uint32_t c = 0; c < (uint32_t)kCandSlots; ++c) cv[c] = c < cm.cnt ? L.cand[j * kCandSlots + c] : 0ull;
+  auto mine = [&](uint64_t v) {
+    for (uint32_t k = 0; k < ln; ++k)
+      if (B.rule_lits[lo + k] == (uint32_t)(v & 0x7FFFFF)) return true;
+    return false;
+  };
+  return bjx::slot_lead_start(cv, cm.cnt, cm.first_inv, rs, rl, back, mine);
 }
 
 // First occurrence at or after p (before end) of one of lead rule R's
@@ -2475,16 +2470,16 @@ __device__ __forceinline__ bool eq_certain(const Bind &B, const Lines &L, uint64
   const DevRule &R = B.rules[r];
   if (!R.equiv || !(R.lead & 2u)) return false;  // equivalent, literals not host-split
   const CandMeta cm = L.cand_meta[j];
-  const uint32_t ns = min(cm.cnt, (uint32_t)kCandSlots);
-  uint64_t need = 0;
-  for (uint32_t k = 0; k < R.lits_len; ++k) need |= 1ull << (B.rule_lits[R.lits_off + k] & 31);
-  for (uint32_t c = 0; c < ns; ++c) {
-    const uint64_t v = L.cand[j * kCandSlots + c];
-    if (!(v & kCandVerified) || (v >> 24) < rs) continue;
+  uint32_t need = 0;
+  for (uint32_t k = 0; k < R.lits_len; ++k) need |= 1u << (B.rule_lits[R.lits_off + k] & 31);
+  uint64_t cv[kCandSlots];
+  for (uint32_t c = 0; c < (uint32_t)kCandSlots; ++c) cv[c] = c < cm.cnt ? L.cand[j * kCandSlots + c] : 0ull;
+  auto mine = [&](uint64_t v) {
     for (uint32_t k = 0; k < R.lits_len; ++k)
       if (B.rule_lits[R.lits_off + k] == (uint32_t)(v & 0x7FFFFF)) return true;
-  }
-  return cm.cnt > (uint32_t)kCandSlots && B.lits_small && L.rest_off[j] <= kCertainGap && ((cm.bits >> 32) & need) != 0;
+    return false;
+  };
+  return bjx::slot_certain(cv, cm.cnt, cm.bits, need, B.lits_small != 0, L.rest_off[j], rs, mine);
 }
 
 // lead_start, then, for a line whose hits overflowed its slots (the start is
@@ -6041,6 +6036,23 @@ static bool split_at_host(const PrefLit &pl, const std::string &h, PrefLit *piec
   return true;
 }
 
+// The literals a bind interns for one compiled rule, in interning order: each
+// prefilter literal (with its host-free piece and the piece's offset when the
+// literal spells the rule's own host `host`), then each anchored prefix.  The
+// bind's rule loop and bjx_debug_ruleset_literals both walk this.
+template <class P, class A>
+static void for_rule_literals(const CompiledRegex &rx, const std::string *host, P pref, A anchor) {
+  if (rx.mode == kModePrefilter)
+    for (const PrefLit &pl : rx.pref) {
+      PrefLit piece;
+      uint32_t off = 0;
+      const bool split = host && split_at_host(pl, *host, &piece, &off);
+      pref(pl, split ? &piece : nullptr, off);
+    }
+  if (rx.mode == kModeAnchored)
+    for (const PrefLit &pl : rx.anchor) anchor(pl);
+}
+
 void bind_ruleset(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *sample, size_t sample_n) {
   if (e->bound_uid == rs->uid && e->bound_dec_version == e->decisions_version) return;
   // DFA job keys: a rule id (windowed jobs r, legacy n_rules + r, null jobs
@@ -6143,28 +6155,25 @@ void bind_ruleset(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *sample, s
       return id;
     };
     d.lits_off = (uint32_t)rule_lits.size();
-    if (r.rx.mode == kModePrefilter)
-      for (auto &pl : r.rx.pref) {
-        // a per-site rule's literal that spells its own host (e.g. "GET <host> GET
-        // /wp-login.php HTTP/") is filed under its longest host-free piece: the
-        // piece is shared by every host's copy of the rule (one gram, one
-        // verification), the line's host id picks the rule (lh_tab), and the full
-        // literal is checked around the hit in k_lines
-        PrefLit piece;
-        uint32_t off = 0;
-        if (site_host[i] && split_at_host(pl, *site_host[i], &piece, &off)) {
-          const uint32_t full = intern_lit(pl, false);
-          rule_lits.push_back(intern_lit(piece, true));
-          rule_full.push_back((full << 8) | off);
-        } else {
-          rule_lits.push_back(intern_lit(pl, true));
-          rule_full.push_back(kNone);
-        }
-      }
-    d.lits_len = (uint16_t)(rule_lits.size() - d.lits_off);
-    d.anc_off = (uint32_t)rule_lits.size();
-    if (r.rx.mode == kModeAnchored)
-      for (auto &pl : r.rx.anchor) { rule_lits.push_back(intern_lit(pl, false)); rule_full.push_back(kNone); }
+    for_rule_literals(r.rx, site_host[i],
+                      [&](const PrefLit &pl, const PrefLit *piece, uint32_t off) {
+                        // a per-site rule's literal that spells its own host (e.g. "GET <host> GET
+                        // /wp-login.php HTTP/") is filed under its longest host-free piece: the
+                        // piece is shared by every host's copy of the rule (one gram, one
+                        // verification), the line's host id picks the rule (lh_tab), and the full
+                        // literal is checked around the hit in k_lines
+                        if (piece) {
+                          const uint32_t full = intern_lit(pl, false);
+                          rule_lits.push_back(intern_lit(*piece, true));
+                          rule_full.push_back((full << 8) | off);
+                        } else {
+                          rule_lits.push_back(intern_lit(pl, true));
+                          rule_full.push_back(kNone);
+                        }
+                        d.lits_len++;
+                      },
+                      [&](const PrefLit &pl) { rule_lits.push_back(intern_lit(pl, false)); rule_full.push_back(kNone); });
+    d.anc_off = d.lits_off + d.lits_len;
     d.anc_len = (uint16_t)(rule_lits.size() - d.anc_off);
     d.anc_equiv = r.rx.anchor_equivalent ? 1 : 0;
     // bit 0: every match of the pattern begins with a literal of pref; bit 1:
@@ -10018,6 +10027,24 @@ extern "C" int bjx_debug_rule_lead(const bjx_ruleset *rs, size_t i) {
   if (!rs || i >= rs->rules.size()) return BJX_ERR_ARG;
   const auto &rx = rs->rules[i].rx;
   return rx.mode == kModePrefilter && rx.pref_lead ? (int)rx.lead_dist : -1;
+}
+
+extern "C" size_t bjx_debug_ruleset_literals(const bjx_ruleset *rs) {
+  if (!rs) return 0;
+  // the bind's interning (intern_lit keys a literal by bytes and case mask),
+  // counted only, over the same walk of each rule's literals
+  std::vector<const std::string *> site_host(rs->rules.size(), nullptr);
+  for (auto &st : rs->sites)
+    for (uint32_t r : st.second) site_host[r] = &st.first;
+  std::set<std::pair<std::string, std::string>> ids;
+  for (size_t i = 0; i < rs->rules.size(); ++i)
+    for_rule_literals(rs->rules[i].rx, site_host[i],
+                      [&](const PrefLit &pl, const PrefLit *piece, uint32_t) {
+                        ids.emplace(pl.s, pl.ci);
+                        if (piece) ids.emplace(piece->s, piece->ci);
+                      },
+                      [&](const PrefLit &pl) { ids.emplace(pl.s, pl.ci); });
+  return ids.size();
 }
 
 extern "C" size_t bjx_debug_rule_literal(const bjx_ruleset *rs, size_t i, char *out, size_t cap) {

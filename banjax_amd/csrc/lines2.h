@@ -222,65 +222,35 @@ __device__ __forceinline__ uint64_t l2_job_rec(const Bind &B, uint32_t r, const 
   const uint32_t lm = ji.x, fl = ji.y, lead = (fl >> 2) & 3u;
   if (fl & (kJiNfa | kJiBigLit)) return kJobLegacy;
   const bool ovf = cm.cnt > (uint32_t)kCandSlots;
-  const uint32_t ns = min(cm.cnt, (uint32_t)kCandSlots);
   auto mine = [&](uint64_t v) {
     const uint32_t id = (uint32_t)(v & 0x7FFFFF);
     return id < 32 && ((lm >> id) & 1u);
   };
-  if ((fl & kJiEquiv) && (lead & 2u)) {  // eq_certain
-#pragma unroll
-    for (uint32_t c = 0; c < (uint32_t)kCandSlots; ++c) {
-      if (c >= ns) break;
-      const uint64_t v = cv[c];
-      if ((v & kCandVerified) && (v >> 24) >= rs && mine(v)) return kJobDecided;
-    }
-    if (ovf && B.lits_small && rest_off <= kCertainGap && ((cm.bits >> 32) & lm) != 0) return kJobDecided;
-  }
+  static_assert(bjx::kSlots == (uint32_t)kCandSlots && bjx::kSlotVerified == kCandVerified && bjx::kSlotCertainGap == kCertainGap,
+                "bjx_common.h's slot arithmetic is CandMeta's");
+  // eq_certain
+  if ((fl & kJiEquiv) && (lead & 2u) && bjx::slot_certain(cv, cm.cnt, cm.bits, lm, B.lits_small != 0, rest_off, rs, mine))
+    return kJobDecided;
   const uint32_t skl = ji.z & 0xFFFFu;
   const uint32_t sk = skl && skl <= rl ? skl : 0u;
   uint32_t st0 = 0;
-  if (lead == 3u && B.cfirst) {
-    // lead_start from the line's first candidate of each of the rule's
-    // literals (rulesets of <= kCandFirstLits literals: exact, overflow or not)
+  if (lead == 3u) {  // lead_start (lead & 1 gates it, lead & 3 == 3 runs it)
     const uint32_t ld = fl >> 16, back = ld ? ld + 3u : 0u;
-    uint64_t f = ~0ull;
-    for (uint32_t m = lm; m; m &= m - 1) {
-      const uint64_t q = cfirst[(uint32_t)__ffs(m) - 1];
-      f = q < f ? q : f;
-    }
-    if (f == ~0ull) st0 = rl;  // none of its literals occurs: no match
-    else {
-      // a first candidate in the header still bounds the first one in rest from below
-      const uint32_t o = f <= rs ? 0u : (uint32_t)min<uint64_t>(f - rs, rl);
-      st0 = o > back ? o - back : 0u;
-    }
-  } else if (lead == 3u) {  // lead_start (lead & 1 gates it, lead & 3 == 3 runs it)
-    const uint32_t ld = fl >> 16, back = ld ? ld + 3u : 0u;
-    uint64_t f = ~0ull;
-#pragma unroll
-    for (uint32_t c = 0; c < (uint32_t)kCandSlots; ++c) {
-      if (c >= ns) break;
-      const uint64_t v = cv[c];
-      const uint64_t q = v >> 24;
-      if (q < rs || q >= f) continue;
-      if (ovf || mine(v)) f = q;
-    }
-    bool zero = false;
-    if (ovf) {
-      const uint64_t mf = cm.first_inv ? (uint64_t)(~cm.first_inv) << 3 : ~0ull;
-      if (mf < rs) zero = true;
-      f = mf < f ? mf : f;
-    }
-    if (!zero) {
-      if (f == ~0ull) st0 = rl;
-      else {
-        const uint32_t o = (uint32_t)min<uint64_t>(f - rs, rl);
-        st0 = o > back ? o - back : 0u;
+    if (B.cfirst) {
+      // from the line's first candidate of each of the rule's literals
+      // (rulesets of <= kCandFirstLits literals: exact, overflow or not)
+      uint64_t f = ~0ull;
+      for (uint32_t m = lm; m; m &= m - 1) {
+        const uint64_t q = cfirst[(uint32_t)__ffs(m) - 1];
+        f = q < f ? q : f;
       }
+      st0 = bjx::lead_bound(f, rs, rl, back);
+    } else {
+      st0 = bjx::slot_lead_start(cv, cm.cnt, cm.first_inv, rs, rl, back, mine);
+      // lead_start_seek: past overflowed slots the start is the first hit of ANY
+      // literal; k_dfa seeks forward to the rule's own
+      if (st0 < rl && ovf) return kJobLegacy;
     }
-    // lead_start_seek: past overflowed slots the start is the first hit of ANY
-    // literal; k_dfa seeks forward to the rule's own
-    if (st0 < rl && ovf) return kJobLegacy;
   }
   if (st0) return rs + st0;
   return (rs + sk) | (sk ? kJobSkipState : 0ull);

@@ -18,6 +18,12 @@ extern "C" {
 int bjx_debug_rule_match_host(const bjx_ruleset *rs, size_t rule_idx, const uint8_t *text, size_t n);
 /* required literal the prefilter uses for a rule (bytes written, full length returned) */
 size_t bjx_debug_rule_literal(const bjx_ruleset *rs, size_t rule_idx, char *out, size_t cap);
+/* Test hook (host only): how many literals a bind of this ruleset interns
+   (prefilter literals, the host-free pieces of host-split ones, anchored
+   prefixes).  At most 8: the scan keeps each literal's first candidate per
+   line (Bind::cfirst); at most 32: a bit of the overflow summary names one
+   literal (Bind::lits_small); ids are given in rule order. */
+size_t bjx_debug_ruleset_literals(const bjx_ruleset *rs);
 /* a prefilter rule whose every match begins within a bounded distance of its
    literals (its DFA jobs start near the first hit): that distance in bytes;
    -1 for every other rule */
@@ -40,7 +46,7 @@ size_t bjx_debug_phase_ms(bjx_engine *e, double *out, size_t cap);
    wave (k_lines), 0 for k_parse_match (returns 5) */
 size_t bjx_debug_kernel_ms(bjx_engine *e, double *out, size_t cap);
 /* last batch: gram bitset hits, recorded literal hits, lines sent to the per-line
-   fallback, lines decided by the long-line pass, DFA jobs; then the state
+   fallback, bytes of the scan's LDS image, DFA jobs; then the state
    tables: IP slots, IPs, state slots, states; then gram table hits, the
    rate-limit grouping (0: full sort by state slot; else two-level, 1 + the
    events of its oversized buckets), rate-limit runs that crossed a k_apply

@@ -201,6 +201,10 @@ def main():
         "malformed headers, exotic ParseFloat tokens, net.ParseIP/CIDR edges, UTF-8, (?i) folding, \\b")
     run("tile_geometry", GEOM_CFG, [(geom_lines(t, 9, n=100), t * S)],
         "line lengths around the scan kernel's 4 KB tile / 512 B halo / 128 lines-per-tile limits")
+    from tests.long_lines import cfg4_tile_start_log
+    run("long_line_hits", W.CFG4.rules_yaml, [(cfg4_tile_start_log(), t * S)],
+        "lines of workload cfg4 that start on a 4,096-byte scan tile's first byte and end within the 512 bytes "
+        "after it, verbatim and on tile starts again (k_scan once recorded their hits twice, DESIGN.md section 7)")
     for wl, n, b, ips in [("cfg1", 3000, 2, 300), ("cfg2", 2000, 2, 200), ("cfg3", 3000, 2, 300),
                           ("cfg4", 40, 1, 10), ("cfg5", 3000, 2, 2500)]:
         y, batches = workload_batches(wl, n, b, ips)
