@@ -45,6 +45,25 @@ BJX_HD int32_t decode_rune_hd(const uint8_t *s, uint64_t n, int *width) {
   return r;
 }
 
+// ------------------------------------------------------------- table sizing (host)
+
+inline uint64_t next_pow2(uint64_t x) {
+  uint64_t p = 1;
+  while (p < x) p <<= 1;
+  return p;
+}
+// Slots of an open-addressing table that holds n entries under a 3/4 load
+// factor with 1024 to spare, and bytes of an IP arena that holds `bytes` twice
+// over: the one sizing rule of growth, expiry and import.
+inline uint64_t table_cap_for(uint64_t n) { return next_pow2(n * 4 / 3 + 1024); }
+inline uint64_t arena_cap_for(uint64_t bytes) { return next_pow2(2 * bytes + 4096); }
+// the rule's value, never below the floor and never above the ceiling (the ceiling wins over a higher floor)
+constexpr uint64_t kNoCeiling = ~0ull;
+inline uint64_t clamp_cap(uint64_t want, uint64_t floor, uint64_t ceiling) {
+  const uint64_t v = want < floor ? floor : want;
+  return v > ceiling ? ceiling : v;
+}
+
 // ------------------------------------------------------------- hashing
 
 BJX_HD uint64_t mix64(uint64_t x) {

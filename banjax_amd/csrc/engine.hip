@@ -4485,551 +4485,6 @@ __global__ void k_final_flags(uint64_t n, uint8_t *__restrict__ f) {
   if (i < n) f[i] &= (kLineError | kLineOld | kLineExempt);
 }
 
-// undo one batch's claims (table overflow): its slots were empty before the
-// batch and no earlier key's probe chain runs through them
-__global__ void k_ip_rollback(uint64_t cap, State S, uint32_t epoch) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= cap) return;
-  const IpSlot v = S.ip[i];
-  if (v.hash != 0 && (v.born == epoch || v.born == 0)) {
-    S.ip[i] = IpSlot{};
-    S.ip_first[i] = 0xFFFFFFFFu;
-  }
-}
-__global__ void k_st_rollback(uint64_t cap, State S) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= cap) return;
-  const bool live = S.st[i].key != 0 && S.st[i].valid != 0;
-  if (S.st[i].key != 0 && !live) S.st[i] = StSlot{};
-  const uint64_t m = __ballot(live);
-  if (m && (threadIdx.x & 63) == (uint32_t)(__ffsll((unsigned long long)m) - 1))
-    atomicAdd((unsigned long long *)&S.counters[2], (unsigned long long)__popcll(m));
-}
-
-// rehash (table growth)
-__global__ void k_rehash_ip(uint64_t old_cap, const IpSlot *__restrict__ o, IpSlot *__restrict__ nt, uint64_t nmask) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= old_cap || o[i].hash == 0) return;
-  uint64_t j = o[i].hash & nmask;
-  for (;;) {
-    const unsigned long long prev = atomicCAS((unsigned long long *)&nt[j].hash, 0ull, (unsigned long long)o[i].hash);
-    if (prev == 0) { nt[j].id = o[i].id; nt[j].born = o[i].born; nt[j].key16 = o[i].key16; return; }
-    j = (j + 1) & nmask;
-  }
-}
-__global__ void k_rehash_st(uint64_t old_cap, const StSlot *__restrict__ o, StSlot *__restrict__ nt, uint64_t nmask) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= old_cap || o[i].key == 0) return;
-  uint64_t j = mix64(o[i].key) & nmask;
-  for (;;) {
-    const unsigned long long prev = atomicCAS((unsigned long long *)&nt[j].key, 0ull, (unsigned long long)o[i].key);
-    if (prev == 0) { nt[j].hits = o[i].hits; nt[j].start = o[i].start; nt[j].valid = o[i].valid; return; }
-    j = (j + 1) & nmask;
-  }
-}
-
-// expiry (bjx_state_expire): a rebuild into fresh tables that drops every
-// state whose window started before the cutoff and every IP left without one.
-// IP ids stay dense and in first-seen order: keep[id] marks the IPs with a
-// surviving state, its exclusive scan is the new id, the scan of the kept
-// lengths the new arena offset.
-__device__ __forceinline__ bool st_survives(const StSlot &v, int64_t cutoff, uint64_t n_ips) {
-  // (an id past n_ips cannot come from a finished batch: never followed)
-  return v.key != 0 && v.valid != 0 && v.start >= cutoff && (v.key >> 24) - 1 < n_ips;
-}
-// grid-stride; cnt[0] += surviving states (one atomic per block)
-__global__ __launch_bounds__(kBlock) void k_exp_mark(uint64_t st_cap, const StSlot *__restrict__ st, int64_t cutoff,
-                                                     uint64_t n_ips, uint32_t *__restrict__ keep,
-                                                     unsigned long long *__restrict__ cnt) {
-  uint64_t n = 0, z = 0;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < st_cap; i += (uint64_t)gridDim.x * blockDim.x) {
-    const StSlot v = st[i];
-    if (st_survives(v, cutoff, n_ips)) {
-      keep[(v.key >> 24) - 1] = 1u;  // every writer stores the same value
-      ++n;
-    }
-  }
-  block_sum2(n, z);
-  if (threadIdx.x == 0 && n) atomicAdd(&cnt[0], (unsigned long long)n);
-}
-// klen[id] = the arena bytes IP id keeps, over [0, n_ips] (the last entry 0:
-// the scans' totals land there)
-__global__ void k_exp_len(uint64_t n_ips, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ ip_len,
-                          uint64_t *__restrict__ klen) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > n_ips) return;
-  klen[i] = i < n_ips && keep[i] ? ip_len[i] : 0;
-}
-// kept IP id -> its bytes, offset and length under the new id
-__global__ void k_exp_arena(uint64_t n_ips, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ nid,
-                            const uint64_t *__restrict__ noff, const uint64_t *__restrict__ o_off,
-                            const uint32_t *__restrict__ o_len, const uint8_t *__restrict__ o_arena, uint64_t o_used,
-                            uint8_t *__restrict__ n_arena, uint64_t n_arena_cap, uint64_t *__restrict__ n_off,
-                            uint32_t *__restrict__ n_len) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_ips || !keep[i]) return;
-  const uint32_t len = o_len[i];
-  const uint64_t so = o_off[i], d = noff[i];
-  if (so + len > o_used || d + len > n_arena_cap) return;  // (not from a finished batch)
-  for (uint32_t k = 0; k < len; ++k) n_arena[d + k] = o_arena[so + k];
-  n_off[nid[i]] = d;
-  n_len[nid[i]] = len;
-}
-__global__ void k_exp_st(uint64_t old_cap, const StSlot *__restrict__ o, int64_t cutoff, uint64_t n_ips,
-                         const uint32_t *__restrict__ nid, StSlot *__restrict__ nt, uint64_t nmask) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= old_cap) return;
-  const StSlot v = o[i];
-  if (!st_survives(v, cutoff, n_ips)) return;
-  const uint64_t key = ((uint64_t)(nid[(v.key >> 24) - 1] + 1) << 24) | (v.key & 0xFFFFFFull);
-  uint64_t j = mix64(key) & nmask;
-  for (;;) {
-    const unsigned long long prev = atomicCAS((unsigned long long *)&nt[j].key, 0ull, (unsigned long long)key);
-    if (prev == 0) { nt[j].hits = v.hits; nt[j].start = v.start; nt[j].valid = v.valid; return; }
-    j = (j + 1) & nmask;
-  }
-}
-__global__ void k_exp_ip(uint64_t old_cap, const IpSlot *__restrict__ o, uint64_t n_ips, const uint32_t *__restrict__ keep,
-                         const uint32_t *__restrict__ nid, IpSlot *__restrict__ nt, uint64_t nmask) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= old_cap) return;
-  const IpSlot v = o[i];
-  if (v.hash == 0 || v.id >= n_ips || !keep[v.id]) return;
-  uint64_t j = v.hash & nmask;
-  for (;;) {
-    const unsigned long long prev = atomicCAS((unsigned long long *)&nt[j].hash, 0ull, (unsigned long long)v.hash);
-    if (prev == 0) { nt[j].id = nid[v.id]; nt[j].born = v.born; nt[j].key16 = v.key16; return; }
-    j = (j + 1) & nmask;
-  }
-}
-__global__ void k_exp_counters(uint64_t *__restrict__ counters, uint64_t ips, uint64_t bytes, uint64_t states) {
-  if (blockIdx.x || threadIdx.x) return;
-  counters[0] = ips;
-  counters[1] = bytes;
-  counters[2] = states;
-}
-
-// snapshot export (bjx_state_export; format: snapshot.h).  keep / nid / noff
-// come from expiry's mark, length and scan passes with min_start_ns as the
-// cutoff.  k_snap_compact gathers the surviving slots, in any order, as
-// (key = new IP id << 24 | name id, index, {hits, start}) and marks the name
-// ids in use; the host sorts the used names and k_snap_remap rewrites the name
-// bits to the canonical index; a radix sort over the key bits in use orders the
-// records by (ip, name); k_snap_gather writes them, k_snap_ips the IP section.
-// One atomic per block and pass (block_alloc); every block runs the same
-// number of passes.
-__global__ __launch_bounds__(kBlock) void k_snap_compact(uint64_t st_cap, const StSlot *__restrict__ st, int64_t cutoff,
-                                                         uint64_t n_ips, const uint32_t *__restrict__ nid, uint32_t n_names,
-                                                         uint32_t *__restrict__ used, unsigned long long *__restrict__ ctr,
-                                                         uint64_t room, uint64_t *__restrict__ keys,
-                                                         uint32_t *__restrict__ idx, int64_t *__restrict__ pay) {
-  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < st_cap; base += (uint64_t)gridDim.x * kBlock) {
-    const uint64_t i = base + threadIdx.x;
-    StSlot v{};
-    bool live = false;
-    if (i < st_cap) {
-      v = st[i];
-      live = st_survives(v, cutoff, n_ips) && (v.key & 0xFFFFFFull) < n_names;
-    }
-    const uint64_t k = block_alloc(ctr, live ? 1 : 0);
-    if (live && k < room) {
-      const uint32_t name = (uint32_t)(v.key & 0xFFFFFFull);
-      used[name] = 1u;  // every writer stores the same value
-      keys[k] = ((uint64_t)nid[(v.key >> 24) - 1] << 24) | name;
-      idx[k] = (uint32_t)k;
-      pay[2 * k] = v.hits;
-      pay[2 * k + 1] = v.start;
-    }
-  }
-}
-__global__ void k_snap_remap(uint64_t n, uint64_t *__restrict__ keys, const uint32_t *__restrict__ remap) {
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const uint64_t v = keys[k];
-  keys[k] = (v & ~0xFFFFFFull) | remap[v & 0xFFFFFFull];
-}
-// sorted (key, index) -> the 24-byte record {u32 ip, u32 name, i64 hits, i64 start} as three words
-__global__ void k_snap_gather(uint64_t n, const uint64_t *__restrict__ keys, const uint32_t *__restrict__ idx,
-                              const int64_t *__restrict__ pay, uint64_t *__restrict__ recs) {
-  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const uint64_t key = keys[j], s = idx[j];
-  if (s >= n) return;  // (a permutation of [0, n): never taken)
-  recs[3 * j] = (key >> 24) | ((key & 0xFFFFFFull) << 32);
-  recs[3 * j + 1] = (uint64_t)pay[2 * s];
-  recs[3 * j + 2] = (uint64_t)pay[2 * s + 1];
-}
-// kept IP id -> its bytes and offset under the new id (k_exp_arena's shape); i = n_ips writes the end offset
-__global__ void k_snap_ips(uint64_t n_ips, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ nid,
-                           const uint64_t *__restrict__ noff, const uint64_t *__restrict__ o_off,
-                           const uint32_t *__restrict__ o_len, const uint8_t *__restrict__ o_arena, uint64_t o_used,
-                           uint64_t kept_ips, uint64_t kept_bytes, uint64_t *__restrict__ out_off,
-                           uint8_t *__restrict__ out_bytes) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > n_ips) return;
-  if (i == n_ips) { out_off[kept_ips] = kept_bytes; return; }
-  if (!keep[i]) return;
-  const uint32_t len = o_len[i];
-  const uint64_t so = o_off[i], d = noff[i];
-  if (so + len > o_used || d + len > kept_bytes || nid[i] >= kept_ips) return;  // (not from a finished batch)
-  for (uint32_t k = 0; k < len; ++k) out_bytes[d + k] = o_arena[so + k];
-  out_off[nid[i]] = d;
-}
-
-// state query (bjx_state_query; filter checks, sort key, name ranks, node
-// merge: state_query.h).  A state that passes the filter becomes a 16-byte
-// candidate {key_desc(primary), ip id << 24 | rank(name)}: ascending order of
-// that 128-bit key is the order of the rows.  k_qry_scan reads the state table
-// once (no ip filter), k_qry_ip probes one key per interned name (ip filter).
-// Selection is an MSB-first radix select, 8 bits a pass: k_qry_hist counts the
-// digits, the host picks the bucket the limit falls into, k_qry_filter moves
-// the buckets below it to the selected rows and that bucket to the next pass's
-// set.  What is left is sorted (two stable 64-bit sorts through an index) and
-// k_qry_rows / k_qry_bytes write the rows.  One atomic per block and pass
-// (block_alloc); every block runs the same number of passes.
-constexpr int kQryItems = 4;  // k_qry_scan: state slots per thread and pass
-struct QFilter {
-  int64_t min_hits, min_start, max_start;
-  uint32_t name;      // name id, kNone: every name
-  uint32_t by_start;  // primary key: 0 hits, 1 start
-};
-// (an id past n_ips or n_names cannot come from a finished batch: never followed, as st_survives)
-__device__ __forceinline__ bool q_pass(const StSlot &v, const QFilter &F, uint64_t n_ips, uint32_t n_names) {
-  const uint32_t name = (uint32_t)(v.key & 0xFFFFFFull);
-  return v.key != 0 && v.valid != 0 && (v.key >> 24) - 1 < n_ips && name < n_names && (F.name == kNone || name == F.name) &&
-         v.hits >= F.min_hits && v.start >= F.min_start && v.start <= F.max_start;
-}
-__device__ __forceinline__ ulonglong2 q_cand(const StSlot &v, const QFilter &F, const uint32_t *__restrict__ rank) {
-  return make_ulonglong2(bjx_query::key_desc(F.by_start ? v.start : v.hits),
-                         (((v.key >> 24) - 1) << 24) | rank[v.key & 0xFFFFFFull]);
-}
-// grid-stride; cnt[0] += passing states (one atomic per block), keep[ip id] = 1;
-// room != 0: the candidates appended at cnt[1]
-__global__ __launch_bounds__(kBlock) void k_qry_scan(uint64_t st_cap, const StSlot *__restrict__ st, QFilter F, uint64_t n_ips,
-                                                     uint32_t n_names, const uint32_t *__restrict__ rank,
-                                                     uint32_t *__restrict__ keep, unsigned long long *__restrict__ cnt,
-                                                     uint64_t room, ulonglong2 *__restrict__ cand) {
-  uint64_t n = 0, z = 0;
-  constexpr uint64_t kTile = (uint64_t)kBlock * kQryItems;  // slots per block and pass: one block_alloc for all of them
-  for (uint64_t base = (uint64_t)blockIdx.x * kTile; base < st_cap; base += (uint64_t)gridDim.x * kTile) {
-    ulonglong2 c[kQryItems];
-    uint32_t mask = 0;  // bit j: slot j of this thread passes (c[j] set)
-#pragma unroll
-    for (int j = 0; j < kQryItems; ++j) {
-      const uint64_t i = base + (uint64_t)j * kBlock + threadIdx.x;
-      c[j] = make_ulonglong2(0, 0);
-      if (i >= st_cap) continue;
-      const StSlot v = st[i];
-      if (!q_pass(v, F, n_ips, n_names)) continue;
-      keep[(v.key >> 24) - 1] = 1u;  // every writer stores the same value
-      if (room) c[j] = q_cand(v, F, rank);
-      mask |= 1u << j;
-    }
-    n += __popc(mask);
-    if (room) {
-      uint64_t k = block_alloc(&cnt[1], __popc(mask));
-#pragma unroll
-      for (int j = 0; j < kQryItems; ++j)
-        if ((mask >> j) & 1u) {
-          if (k < room) cand[k] = c[j];
-          ++k;
-        }
-    }
-  }
-  block_sum2(n, z);
-  if (threadIdx.x == 0 && n) atomicAdd(&cnt[0], (unsigned long long)n);
-}
-// Get(ip): the IP as k_state_get finds it (hash, probe chain, length and arena
-// bytes), then one lane per interned name id probes ((id + 1) << 24) | name
-__global__ __launch_bounds__(kBlock) void k_qry_ip(State S, uint64_t h, const uint8_t *__restrict__ ip, uint32_t len, QFilter F,
-                                                   uint64_t n_ips, uint32_t n_names, const uint32_t *__restrict__ rank,
-                                                   unsigned long long *__restrict__ cnt, uint64_t room,
-                                                   ulonglong2 *__restrict__ cand) {
-  __shared__ uint32_t s_id;
-  if (threadIdx.x == 0) {
-    uint32_t id = kNone;
-    for (uint64_t i = h & S.ip_mask;; i = (i + 1) & S.ip_mask) {
-      const uint64_t cur = S.ip[i].hash;
-      if (cur == 0) break;
-      if (cur == h) {
-        const uint32_t c = S.ip[i].id;
-        if (c < n_ips && S.ip_len[c] == len && bytes_eq(S.arena + S.ip_off[c], ip, len)) { id = c; break; }
-      }
-    }
-    s_id = id;
-  }
-  __syncthreads();
-  const uint32_t id = s_id;
-  uint64_t n = 0, z = 0;
-  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n_names; base += (uint64_t)gridDim.x * kBlock) {
-    const uint64_t name = base + threadIdx.x;
-    StSlot v{};
-    bool ok = false;
-    if (id != kNone && name < n_names && (F.name == kNone || name == F.name)) {
-      const uint64_t key = ((uint64_t)(id + 1) << 24) | name;
-      for (uint64_t j = mix64(key) & S.st_mask;; j = (j + 1) & S.st_mask) {
-        const uint64_t k = S.st[j].key;
-        if (k == 0) break;
-        if (k == key) {
-          v = S.st[j];
-          ok = q_pass(v, F, n_ips, n_names);
-          break;
-        }
-      }
-    }
-    if (ok) ++n;
-    if (room) {
-      const uint64_t k = block_alloc(&cnt[1], ok ? 1 : 0);
-      if (ok && k < room) cand[k] = q_cand(v, F, rank);
-    }
-  }
-  block_sum2(n, z);
-  if (threadIdx.x == 0 && n) atomicAdd(&cnt[0], (unsigned long long)n);
-}
-__device__ __forceinline__ uint32_t q_digit(const ulonglong2 &c, uint32_t word, uint32_t shift) {
-  return (uint32_t)(((word ? c.y : c.x) >> shift) & 0xFFu);
-}
-// hist[d] += candidates whose digit (8 bits at `shift` of word 0 primary / 1
-// tie) is d.  A thread counts a run of equal digits before it touches LDS: the
-// high bytes of small hit counts are all one value.
-__global__ __launch_bounds__(kBlock) void k_qry_hist(const ulonglong2 *__restrict__ c, uint64_t n, uint32_t word, uint32_t shift,
-                                                     unsigned long long *__restrict__ hist) {
-  static_assert(kBlock == 256, "one histogram bin per thread");
-  __shared__ uint32_t s_h[256];
-  s_h[threadIdx.x] = 0;
-  __syncthreads();
-  uint32_t run_d = 0, run_n = 0;
-  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-    const uint32_t d = q_digit(c[i], word, shift);
-    if (d != run_d && run_n) {
-      atomicAdd(&s_h[run_d], run_n);
-      run_n = 0;
-    }
-    run_d = d;
-    ++run_n;
-  }
-  if (run_n) atomicAdd(&s_h[run_d], run_n);
-  __syncthreads();
-  if (s_h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)s_h[threadIdx.x]);
-}
-// digit < b: selected (appended at ctr[0]); digit == b: the next pass's set (at ctr[1]); above: dropped
-__global__ __launch_bounds__(kBlock) void k_qry_filter(const ulonglong2 *__restrict__ c, uint64_t n, uint32_t word, uint32_t shift,
-                                                       uint32_t b, ulonglong2 *__restrict__ sel, uint64_t sel_room,
-                                                       ulonglong2 *__restrict__ nxt, uint64_t nxt_room,
-                                                       unsigned long long *__restrict__ ctr) {
-  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n; base += (uint64_t)gridDim.x * kBlock) {
-    const uint64_t i = base + threadIdx.x;
-    ulonglong2 v = make_ulonglong2(0, 0);
-    uint32_t d = 256;
-    if (i < n) {
-      v = c[i];
-      d = q_digit(v, word, shift);
-    }
-    const uint64_t k0 = block_alloc(&ctr[0], d < b ? 1 : 0);
-    if (d < b && k0 < sel_room) sel[k0] = v;
-    const uint64_t k1 = block_alloc(&ctr[1], d == b ? 1 : 0);
-    if (d == b && k1 < nxt_room) nxt[k1] = v;
-  }
-}
-__global__ void k_qry_split(uint64_t n, const ulonglong2 *__restrict__ c, uint64_t *__restrict__ tie, uint32_t *__restrict__ idx) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  tie[i] = c[i].y;
-  idx[i] = (uint32_t)i;
-}
-__global__ void k_qry_prim(uint64_t n, const ulonglong2 *__restrict__ c, const uint32_t *__restrict__ idx,
-                           uint64_t *__restrict__ prim) {
-  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const uint32_t s = idx[j];
-  prim[j] = s < n ? c[s].x : ~0ull;  // (a permutation of [0, n): always inside)
-}
-// row r = the r-th candidate in order: its state read back from the table,
-// the lengths of its IP and name; lens[r] = the bytes it takes ([0, n_rows]:
-// the last entry 0, the scan's total lands there)
-__global__ void k_qry_rows(uint64_t n_rows, uint64_t n_cand, const ulonglong2 *__restrict__ c, const uint32_t *__restrict__ idx,
-                           State S, uint64_t n_ips, uint32_t n_names, const uint32_t *__restrict__ by_rank,
-                           const uint64_t *__restrict__ name_off, bjx_state_row *__restrict__ rows,
-                           uint64_t *__restrict__ lens) {
-  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r > n_rows) return;
-  if (r == n_rows) { lens[r] = 0; return; }
-  bjx_state_row o{};
-  const uint32_t s = idx[r];
-  if (s < n_cand) {
-    const uint64_t tie = c[s].y, id = tie >> 24;
-    const uint32_t rk = (uint32_t)(tie & 0xFFFFFFull);
-    if (id < n_ips && rk < n_names) {
-      const uint64_t key = ((id + 1) << 24) | by_rank[rk];
-      for (uint64_t j = mix64(key) & S.st_mask;; j = (j + 1) & S.st_mask) {
-        const uint64_t k = S.st[j].key;
-        if (k == 0) break;
-        if (k == key) { o.hits = S.st[j].hits; o.start_ns = S.st[j].start; break; }
-      }
-      o.ip_len = S.ip_len[id];
-      o.name_len = (uint32_t)(name_off[rk + 1] - name_off[rk]);
-    }
-  }
-  rows[r] = o;
-  lens[r] = (uint64_t)o.ip_len + o.name_len;
-}
-// the rows' offsets and their bytes: IP, then name, at offs[r]
-__global__ void k_qry_bytes(uint64_t n_rows, uint64_t n_cand, const ulonglong2 *__restrict__ c, const uint32_t *__restrict__ idx,
-                            State S, uint64_t n_ips, uint64_t arena_used, const uint64_t *__restrict__ name_off,
-                            const uint8_t *__restrict__ name_bytes, const uint64_t *__restrict__ offs, uint64_t total,
-                            bjx_state_row *__restrict__ rows, uint8_t *__restrict__ out) {
-  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_rows) return;
-  const uint32_t s = idx[r];
-  const uint32_t il = rows[r].ip_len, nl = rows[r].name_len;
-  const uint64_t d = offs[r];
-  rows[r].ip_off = d;
-  rows[r].name_off = d + il;
-  if (s >= n_cand || d + il + nl > total) return;  // (not from a finished batch)
-  const uint64_t tie = c[s].y, id = tie >> 24;
-  if (id >= n_ips) return;
-  const uint64_t so = S.ip_off[id];
-  if (so + il > arena_used) return;
-  for (uint32_t k = 0; k < il; ++k) out[d + k] = S.arena[so + k];
-  if (!nl) return;  // (nl != 0: k_qry_rows found the rank inside the table)
-  const uint64_t no = name_off[tie & 0xFFFFFFull];
-  for (uint32_t k = 0; k < nl; ++k) out[d + il + k] = name_bytes[no + k];
-}
-
-// snapshot import (bjx_state_import).  err[c] = 1 (plain stores of one value)
-// when check c fails: 1 ip_off not monotone from 0, 2 ip_off[n_ips] !=
-// ip_bytes, 3 record ip >= n_ips, 4 record name >= n_names, 5 records not
-// strictly ascending, 6 an IP without a record (the records are sorted by IP,
-// so that is a first IP other than 0, a step over an index, or a last IP other
-// than n_ips - 1), 0 (k_imp_verify) an IP found twice or not under its own id.
-__global__ void k_imp_check(uint64_t n_ips, const uint64_t *__restrict__ ip_off, uint64_t ip_bytes, uint64_t n_states,
-                            const uint64_t *__restrict__ recs, uint32_t n_names, uint32_t *__restrict__ used,
-                            uint32_t *__restrict__ err) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i <= n_ips) {
-    const uint64_t a = ip_off[i];
-    if (i == 0 && a != 0) err[1] = 1u;
-    if (i == n_ips) {
-      if (a != ip_bytes) err[2] = 1u;
-    } else {
-      const uint64_t b = ip_off[i + 1];
-      if (b < a || b - a > 0x7FFFFFFFull) err[1] = 1u;
-    }
-  }
-  if (i < n_states) {
-    const uint64_t w = recs[3 * i];
-    const uint32_t ip = (uint32_t)w, nm = (uint32_t)(w >> 32);
-    if (ip >= n_ips) err[3] = 1u;
-    if (nm >= n_names) err[4] = 1u;
-    else used[nm] = 1u;
-    if (i) {
-      const uint64_t pw = recs[3 * (i - 1)];
-      const uint32_t pip = (uint32_t)pw, pnm = (uint32_t)(pw >> 32);
-      if (ip < pip || (ip == pip && nm <= pnm)) err[5] = 1u;
-      else if (ip - pip > 1) err[6] = 1u;
-    } else if (ip != 0) {
-      err[6] = 1u;
-    }
-    if (i == n_states - 1 && (uint64_t)ip + 1 != n_ips) err[6] = 1u;
-  }
-}
-// per IP: hash_bytes of its bytes, the owner filter, the arena bytes it keeps ([0, n_ips]: the last entry 0)
-__global__ void k_imp_ip(uint64_t n_ips, const uint64_t *__restrict__ ip_off, const uint8_t *__restrict__ bytes,
-                         uint32_t part, uint32_t n_parts, uint32_t *__restrict__ keep, uint64_t *__restrict__ klen,
-                         uint64_t *__restrict__ hash) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > n_ips) return;
-  if (i == n_ips) { keep[i] = 0; klen[i] = 0; hash[i] = 0; return; }
-  const uint64_t a = ip_off[i];
-  const uint32_t len = (uint32_t)(ip_off[i + 1] - a);
-  const uint64_t h = hash_bytes(bytes + a, len);
-  const bool mine = (uint32_t)((h >> 32) % n_parts) == part;  // the node's owner function (part_line)
-  keep[i] = mine ? 1u : 0u;
-  klen[i] = mine ? len : 0;
-  hash[i] = h;
-}
-// cnt[0] += records of kept IPs (one atomic per block)
-__global__ __launch_bounds__(kBlock) void k_imp_count(uint64_t n_states, const uint64_t *__restrict__ recs,
-                                                      const uint32_t *__restrict__ keep,
-                                                      unsigned long long *__restrict__ cnt) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  uint64_t n = i < n_states && keep[(uint32_t)recs[3 * i]] ? 1 : 0, z = 0;
-  block_sum2(n, z);
-  if (threadIdx.x == 0 && n) atomicAdd(&cnt[0], (unsigned long long)n);
-}
-// kept IP -> arena bytes, offset, length and its IpSlot (CAS on an empty slot,
-// as k_exp_ip: equal hashes of distinct IPs take successive slots)
-__global__ void k_imp_place(uint64_t n_ips, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ nid,
-                            const uint64_t *__restrict__ noff, const uint64_t *__restrict__ hash, uint64_t hmask,
-                            const uint64_t *__restrict__ ip_off, const uint8_t *__restrict__ bytes, uint32_t born,
-                            uint64_t kept_ips, uint8_t *__restrict__ n_arena, uint64_t n_arena_cap,
-                            uint64_t *__restrict__ n_off, uint32_t *__restrict__ n_len, IpSlot *__restrict__ nt,
-                            uint64_t nmask) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_ips || !keep[i]) return;
-  const uint64_t a = ip_off[i], d = noff[i];
-  const uint32_t len = (uint32_t)(ip_off[i + 1] - a), id = nid[i];
-  if (id >= kept_ips || d + len > n_arena_cap) return;  // (the scans' totals sized both: never taken)
-  const uint8_t *src = bytes + a;
-  for (uint32_t k = 0; k < len; ++k) n_arena[d + k] = src[k];
-  n_off[id] = d;
-  n_len[id] = len;
-  const uint64_t h = hmask ? (hash[i] & hmask) | 1ull : hash[i];
-  uint64_t j = h & nmask;
-  for (;;) {
-    const unsigned long long prev = atomicCAS((unsigned long long *)&nt[j].hash, 0ull, (unsigned long long)h);
-    if (prev == 0) { nt[j].id = id; nt[j].born = born; nt[j].key16 = ip_key16_bytes(src, len); return; }
-    j = (j + 1) & nmask;
-  }
-}
-// one lane per record of a kept IP (CAS on the key, as k_exp_st)
-__global__ void k_imp_st(uint64_t n_states, const uint64_t *__restrict__ recs, const uint32_t *__restrict__ keep,
-                         const uint32_t *__restrict__ nid, const uint32_t *__restrict__ remap, StSlot *__restrict__ nt,
-                         uint64_t nmask) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_states) return;
-  const uint64_t w = recs[3 * i];
-  const uint32_t ip = (uint32_t)w;
-  if (!keep[ip]) return;
-  const uint64_t key = ((uint64_t)(nid[ip] + 1) << 24) | remap[w >> 32];
-  uint64_t j = mix64(key) & nmask;
-  for (;;) {
-    const unsigned long long prev = atomicCAS((unsigned long long *)&nt[j].key, 0ull, (unsigned long long)key);
-    if (prev == 0) { nt[j].hits = (int64_t)recs[3 * i + 1]; nt[j].start = (int64_t)recs[3 * i + 2]; nt[j].valid = 1; return; }
-    j = (j + 1) & nmask;
-  }
-}
-// every imported IP looked up as ip_claim_line looks up an IP of an earlier
-// batch (hash, key16, arena bytes past 15), along its whole probe chain: it
-// must match one slot, the one with its own id
-__global__ void k_imp_verify(uint64_t n_ips, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ nid,
-                             const uint64_t *__restrict__ hash, uint64_t hmask, const uint64_t *__restrict__ ip_off,
-                             const uint8_t *__restrict__ bytes, uint64_t kept_ips, const IpSlot *__restrict__ nt,
-                             uint64_t nmask, const uint64_t *__restrict__ n_off, const uint32_t *__restrict__ n_len,
-                             const uint8_t *__restrict__ n_arena, uint32_t *__restrict__ err) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_ips || !keep[i]) return;
-  const uint64_t a = ip_off[i];
-  const uint32_t len = (uint32_t)(ip_off[i + 1] - a);
-  const uint8_t *src = bytes + a;
-  const uint4 k16 = ip_key16_bytes(src, len);
-  const uint64_t h = hmask ? (hash[i] & hmask) | 1ull : hash[i];
-  uint32_t found = 0;
-  bool own = false;
-  uint64_t j = h & nmask;
-  for (uint64_t step = 0; step <= nmask; ++step) {
-    const IpSlot v = nt[j];
-    if (v.hash == 0) break;
-    if (v.hash == h && v.id < kept_ips && key16_eq(v.key16, k16) &&
-        (len <= 15 || (n_len[v.id] == len && bytes_eq(n_arena + n_off[v.id], src, len)))) {
-      ++found;
-      own = own || v.id == nid[i];
-    }
-    j = (j + 1) & nmask;
-  }
-  if (found != 1 || !own) err[0] = 1u;
-}
-
 // --------------------------------------------------------------- multi-GPU exchange
 // The partition runs over the lines in tiles of `steps` x kBlock lines (one
 // block each, one line per lane per step), in line order: k_part_count sums
@@ -5359,34 +4814,6 @@ __global__ void k_scatter_outcomes(uint64_t n, const uint32_t *__restrict__ src,
   if (k < n) out[src[k]] = in[k];
 }
 
-// state query (RegexRateLimitStates.Get for one (ip, name))
-__global__ void k_state_get(State S, uint64_t h, const uint8_t *ip, uint32_t len, uint32_t name_id, int64_t *out) {
-  out[0] = 0;
-  uint64_t i = h & S.ip_mask;
-  for (;;) {
-    const uint64_t cur = S.ip[i].hash;
-    if (cur == 0) return;
-    if (cur == h) {
-      const uint32_t id = S.ip[i].id;
-      if (S.ip_len[id] == len && bytes_eq(S.arena + S.ip_off[id], ip, len)) {
-        const uint64_t key = ((uint64_t)(id + 1) << 24) | name_id;
-        uint64_t j = mix64(key) & S.st_mask;
-        for (;;) {
-          const uint64_t k = S.st[j].key;
-          if (k == 0) { out[0] = 1; return; }  // ip known, rule state absent
-          if (k == key) {
-            if (!S.st[j].valid) { out[0] = 1; return; }
-            out[0] = 2; out[1] = S.st[j].hits; out[2] = S.st[j].start;
-            return;
-          }
-          j = (j + 1) & S.st_mask;
-        }
-      }
-    }
-    i = (i + 1) & S.ip_mask;
-  }
-}
-
 // =====================================================================
 //                               host side
 // =====================================================================
@@ -5454,12 +4881,6 @@ struct HostBuf {
 };
 
 inline unsigned grid_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
-uint64_t next_pow2(uint64_t x) {
-  uint64_t p = 1;
-  while (p < x) p <<= 1;
-  return p;
-}
 
 }  // namespace
 
@@ -7224,38 +6645,6 @@ void bind_ruleset(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *sample, s
   e->bound_dec_version = e->decisions_version;
 }
 
-void alloc_state(bjx_engine *e, uint64_t ip_cap, uint64_t st_cap, uint64_t arena_cap) {
-  State &S = e->S;
-  HIP_OK(hipMalloc(&S.ip, ip_cap * sizeof(IpSlot)));
-  HIP_OK(hipMalloc(&S.ip_first, ip_cap * 4));
-  HIP_OK(hipMalloc(&S.ip_off, ip_cap * 8));
-  HIP_OK(hipMalloc(&S.ip_len, ip_cap * 4));
-  HIP_OK(hipMalloc(&S.arena, arena_cap));
-  HIP_OK(hipMalloc(&S.st, st_cap * sizeof(StSlot)));
-  HIP_OK(hipMalloc(&S.counters, kCounterBytes));
-  HIP_OK(hipMemset(S.ip, 0, ip_cap * sizeof(IpSlot)));
-  HIP_OK(hipMemset(S.ip_first, 0xFF, ip_cap * 4));
-  HIP_OK(hipMemset(S.st, 0, st_cap * sizeof(StSlot)));
-  HIP_OK(hipMemset(S.counters, 0, kCounterBytes));
-  HIP_OK(hipMalloc(&S.ip_st, ip_cap * 4));
-  HIP_OK(hipMemset(S.ip_st, 0xFF, ip_cap * 4));
-  S.ip_st_cap = ip_cap;
-  S.hot_name = kNone;
-  S.ip_mask = ip_cap - 1;
-  S.st_mask = st_cap - 1;
-  S.arena_cap = arena_cap;
-  e->ip_cap = ip_cap;
-  e->st_cap = st_cap;
-}
-
-void free_state(bjx_engine *e) {
-  State &S = e->S;
-  for (void *p : {(void *)S.ip, (void *)S.ip_first, (void *)S.ip_off, (void *)S.ip_len, (void *)S.arena, (void *)S.st,
-                  (void *)S.counters, (void *)S.ip_st})
-    if (p) (void)hipFree(p);
-  S = State{};
-}
-
 // the sorted records' event index words and their stride, in the form the
 // last rate-limit stage used
 static const uint32_t *ev_words(const bjx_engine *e) {
@@ -7286,78 +6675,6 @@ void read_counters(bjx_engine *e) {
   pin_sync(e);
 }
 
-// rehash the IP table into one that holds `want` IPs under a 3/4 load factor
-void grow_ip(bjx_engine *e, uint64_t want) {
-  State &S = e->S;
-  const uint64_t n_ips = e->host_counters[0];
-  const uint64_t cap = next_pow2(want * 4 / 3 + 1024);
-  if (cap <= e->ip_cap) return;
-  IpSlot *nt; uint32_t *nf; uint64_t *noff; uint32_t *nlen;
-  HIP_OK(hipMalloc(&nt, cap * sizeof(IpSlot)));
-  HIP_OK(hipMalloc(&nf, cap * 4));
-  HIP_OK(hipMalloc(&noff, cap * 8));
-  HIP_OK(hipMalloc(&nlen, cap * 4));
-  HIP_OK(hipMemsetAsync(nt, 0, cap * sizeof(IpSlot), e->stream));
-  HIP_OK(hipMemsetAsync(nf, 0xFF, cap * 4, e->stream));
-  HIP_OK(hipMemcpyAsync(noff, S.ip_off, n_ips * 8, hipMemcpyDeviceToDevice, e->stream));
-  HIP_OK(hipMemcpyAsync(nlen, S.ip_len, n_ips * 4, hipMemcpyDeviceToDevice, e->stream));
-  hipLaunchKernelGGL(k_rehash_ip, dim3(grid_for(e->ip_cap)), dim3(kBlock), 0, e->stream, e->ip_cap, S.ip, nt, cap - 1);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipStreamSynchronize(e->stream));
-  (void)hipFree(S.ip); (void)hipFree(S.ip_first); (void)hipFree(S.ip_off); (void)hipFree(S.ip_len);
-  S.ip = nt; S.ip_first = nf; S.ip_off = noff; S.ip_len = nlen;
-  S.ip_mask = cap - 1;
-  (void)hipFree(S.ip_st);
-  HIP_OK(hipMalloc(&S.ip_st, cap * 4));
-  HIP_OK(hipMemsetAsync(S.ip_st, 0xFF, cap * 4, e->stream));
-  S.ip_st_cap = cap;
-  e->ip_cap = cap;
-  ++e->rehashes;
-}
-
-// rehash the state table into one that holds `want` states under a 3/4 load factor
-void grow_st(bjx_engine *e, uint64_t want) {
-  State &S = e->S;
-  const uint64_t cap = next_pow2(want * 4 / 3 + 1024);
-  if (cap <= e->st_cap) return;
-  StSlot *nt;
-  HIP_OK(hipMalloc(&nt, cap * sizeof(StSlot)));
-  HIP_OK(hipMemsetAsync(nt, 0, cap * sizeof(StSlot), e->stream));
-  hipLaunchKernelGGL(k_rehash_st, dim3(grid_for(e->st_cap)), dim3(kBlock), 0, e->stream, e->st_cap, S.st, nt, cap - 1);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipStreamSynchronize(e->stream));
-  (void)hipFree(S.st);
-  S.st = nt;
-  S.st_mask = cap - 1;
-  HIP_OK(hipMemsetAsync(S.ip_st, 0xFF, S.ip_st_cap * 4, e->stream));  // slots moved
-  if (cap > (1ull << 32)) S.hot_name = kNone;
-  e->st_cap = cap;
-  ++e->rehashes;
-}
-
-// Tables sized for the steady state, not for every batch's worst case: the
-// IP and state tables keep room for `new_ips` / `new_states` more entries
-// (claims beyond that roll back and grow, see rate_limit_stage); the arena
-// always fits the batch's IP bytes.  Small tables keep the random probes in
-// cache and the state-slot sort short.
-// (e->host_counters current: the caller has just read them)
-void ensure_capacity(bjx_engine *e, uint64_t new_ips, uint64_t new_bytes, uint64_t new_states) {
-  State &S = e->S;
-  const uint64_t n_ips = e->host_counters[0], used = e->host_counters[1], n_st = e->host_counters[2];
-  if ((n_ips + new_ips) * 4 > e->ip_cap * 3) grow_ip(e, 2 * (n_ips + new_ips));
-  if (used + new_bytes > S.arena_cap) {
-    const uint64_t cap = std::max<uint64_t>(S.arena_cap * 2, used + new_bytes + (1 << 20));
-    uint8_t *na;
-    HIP_OK(hipMalloc(&na, cap));
-    HIP_OK(hipMemcpyAsync(na, S.arena, used, hipMemcpyDeviceToDevice, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    (void)hipFree(S.arena);
-    S.arena = na;
-    S.arena_cap = cap;
-  }
-  if ((n_st + new_states) * 4 > e->st_cap * 3) grow_st(e, 2 * (n_st + new_states));
-}
-
 template <typename F>
 void cub_call(bjx_engine *e, F f) {
   size_t bytes = 0;
@@ -7373,6 +6690,33 @@ int bit_width(uint64_t x) {
 }
 
 }  // namespace
+
+// Every entry point that takes an engine: the lock, the device, f, and its
+// errors as a code with the message kept for bjx_engine_last_error.  A throw
+// may have left reads queued into the frames it unwound and counters marked
+// fresh that a later stage would trust: both are dropped.
+template <typename F>
+static int guarded(bjx_engine *e, F f) {
+  if (!e) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  int code;
+  try {
+    HIP_OK(hipSetDevice(e->device));
+    return f();
+  } catch (const BjxError &x) {
+    e->last_error = x.what();
+    code = x.code;
+  } catch (const std::bad_alloc &) {
+    e->last_error = "host out of memory";
+    code = BJX_ERR_NOMEM;
+  }
+  e->pin_n = e->pin_used = 0;
+  e->counters_fresh = false;
+  return code;
+}
+
+// the state path: rollback, growth, clear, expiry, snapshot, query
+#include "state_ops.h"
 
 extern "C" int bjx_engine_create(int device, const bjx_engine_options *opts, bjx_engine **out, char *err, size_t err_len) {
   if (!out) return BJX_ERR_ARG;
@@ -8680,37 +8024,14 @@ static void run_batch(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *bytes
 
 extern "C" int bjx_process_batch(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *bytes, size_t n, int64_t now_ns,
                                  uint32_t flags, bjx_batch_result *out) {
-  if (!e || !rs || !out || (n && !bytes)) return BJX_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
-  try {
+  if (!rs || !out || (n && !bytes)) return BJX_ERR_ARG;
+  return guarded(e, [&]() -> int {
     run_batch(e, rs, bytes, n, now_ns, flags, out);
     return BJX_OK;
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return x.code;
-  } catch (const std::bad_alloc &) {
-    e->last_error = "host out of memory";
-    return BJX_ERR_NOMEM;
-  }
+  });
 }
 
 // ------------------------------------------------------------ multi-GPU batch
-
-template <typename F>
-static int guarded(bjx_engine *e, F f) {
-  if (!e) return BJX_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
-  try {
-    HIP_OK(hipSetDevice(e->device));
-    return f();
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return x.code;
-  } catch (const std::bad_alloc &) {
-    e->last_error = "host out of memory";
-    return BJX_ERR_NOMEM;
-  }
-}
 
 extern "C" int bjx_match_batch(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *bytes, size_t n, int64_t now_ns,
                                uint32_t flags, bjx_batch_result *out) {
@@ -9048,917 +8369,6 @@ extern "C" int bjx_batch_bans(bjx_engine *e, bjx_ban_batch *out) {
     out->ip_off = e->ban_ipo.data();
     return BJX_OK;
   });
-}
-
-extern "C" int bjx_state_get(bjx_engine *e, const char *ip, size_t ip_len, const char *name, size_t name_len,
-                             int64_t *num_hits, int64_t *start_ns) {
-  if (!e || (ip_len && !ip)) return BJX_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
-  try {
-    HIP_OK(hipSetDevice(e->device));
-    auto it = e->name_ids.find(std::string(name ? name : "", name_len));
-    if (it == e->name_ids.end()) return 0;
-    e->q_ip.ensure(ip_len + 1);
-    e->q_out.ensure(4);
-    if (ip_len) HIP_OK(hipMemcpyAsync(e->q_ip.p, ip, ip_len, hipMemcpyHostToDevice, e->stream));
-    uint64_t h = hash_bytes(reinterpret_cast<const uint8_t *>(ip), (uint32_t)ip_len);
-    if (e->dbg_hash_mask) h = (h & e->dbg_hash_mask) | 1;
-    hipLaunchKernelGGL(k_state_get, dim3(1), dim3(1), 0, e->stream, e->S, h, e->q_ip.p, (uint32_t)ip_len, it->second, e->q_out.p);
-    HIP_OK(hipGetLastError());
-    int64_t o[3];
-    HIP_OK(hipMemcpyAsync(o, e->q_out.p, 24, hipMemcpyDeviceToHost, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    if (o[0] != 2) return 0;
-    if (num_hits) *num_hits = o[1];
-    if (start_ns) *start_ns = o[2];
-    return 1;
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return x.code;
-  }
-}
-
-extern "C" int64_t bjx_state_len(bjx_engine *e) {
-  if (!e) return BJX_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
-  try {
-    HIP_OK(hipSetDevice(e->device));
-    read_counters(e);
-    return (int64_t)e->host_counters[0];
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return x.code;
-  }
-}
-
-extern "C" int bjx_state_stats_get(bjx_engine *e, bjx_state_stats *out) {
-  if (!e || !out) return BJX_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
-  try {
-    HIP_OK(hipSetDevice(e->device));
-    read_counters(e);
-    out->ips = e->host_counters[0];
-    out->ip_slots = e->ip_cap;
-    out->states = e->host_counters[2];
-    out->state_slots = e->st_cap;
-    out->arena_bytes = e->host_counters[1];
-    out->arena_capacity = e->S.arena_cap;
-    out->device_bytes = e->ip_cap * (sizeof(IpSlot) + 4 + 8 + 4) + e->st_cap * sizeof(StSlot) + e->S.arena_cap;
-    out->rehashes = e->rehashes;
-    return BJX_OK;
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return x.code;
-  }
-}
-
-// live keys left in the state / IP tables (bjx_state_clear's check)
-__global__ void k_count_live(const StSlot *__restrict__ st, uint64_t st_cap, const IpSlot *__restrict__ ip, uint64_t ip_cap,
-                             unsigned long long *__restrict__ cnt) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < st_cap && st[i].key != 0) atomicAdd(&cnt[0], 1ull);
-  if (i < ip_cap && ip[i].hash != 0) atomicAdd(&cnt[1], 1ull);
-}
-
-extern "C" int bjx_state_clear(bjx_engine *e) {
-  if (!e) return BJX_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
-  try {
-    HIP_OK(hipSetDevice(e->device));
-    HIP_OK(hipDeviceSynchronize());  // nothing of an earlier batch may land after the clear
-    e->sort2_hold = 0;
-    HIP_OK(hipMemsetAsync(e->S.ip, 0, e->ip_cap * sizeof(IpSlot), e->stream));
-    HIP_OK(hipMemsetAsync(e->S.ip_first, 0xFF, e->ip_cap * 4, e->stream));
-    HIP_OK(hipMemsetAsync(e->S.st, 0, e->st_cap * sizeof(StSlot), e->stream));
-    HIP_OK(hipMemsetAsync(e->S.counters, 0, kCounterBytes, e->stream));
-    HIP_OK(hipMemsetAsync(e->S.ip_st, 0xFF, e->S.ip_st_cap * 4, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    {
-      // the tables must read back empty: IP ids restart at 0, so a state slot
-      // that survived would be found again by a new IP's key
-      e->chk.ensure(8);
-      HIP_OK(hipMemsetAsync(e->chk.p, 0, 16, e->stream));
-      const uint64_t n = std::max(e->st_cap, e->ip_cap);
-      hipLaunchKernelGGL(k_count_live, dim3(grid_for(n)), dim3(kBlock), 0, e->stream, e->S.st, e->st_cap, e->S.ip, e->ip_cap,
-                         e->chk.p);
-      HIP_OK(hipGetLastError());
-      unsigned long long live[2] = {0, 0};
-      HIP_OK(hipMemcpyAsync(live, e->chk.p, 16, hipMemcpyDeviceToHost, e->stream));
-      HIP_OK(hipStreamSynchronize(e->stream));
-      if (live[0] | live[1]) {
-        fprintf(stderr, "[bjx] state_clear: %llu state slots and %llu IP slots survived the clear; clearing again\n", live[0],
-                live[1]);
-        HIP_OK(hipDeviceSynchronize());
-        HIP_OK(hipMemset(e->S.st, 0, e->st_cap * sizeof(StSlot)));
-        HIP_OK(hipMemset(e->S.ip, 0, e->ip_cap * sizeof(IpSlot)));
-        HIP_OK(hipDeviceSynchronize());
-      }
-    }
-    return BJX_OK;
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return x.code;
-  }
-}
-
-namespace {
-uint64_t state_device_bytes(uint64_t ip_cap, uint64_t st_cap, uint64_t arena_cap) {
-  return ip_cap * (sizeof(IpSlot) + 4 + 8 + 4) + st_cap * sizeof(StSlot) + arena_cap;
-}
-// device allocations of one expiry: freed on every way out unless taken
-struct ExpAlloc {
-  std::vector<void *> ptrs;
-  bool nomem = false;
-  template <typename T>
-  T *get(uint64_t n) {
-    void *p = nullptr;
-    if (nomem) return nullptr;
-    if (hipMalloc(&p, std::max<uint64_t>(n, 1) * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();  // the failed allocation is reported as BJX_ERR_NOMEM, not left pending
-      nomem = true;
-      return nullptr;
-    }
-    ptrs.push_back(p);
-    return static_cast<T *>(p);
-  }
-  void take() { ptrs.clear(); }
-  ~ExpAlloc() {
-    for (void *p : ptrs) (void)hipFree(p);
-  }
-};
-}  // namespace
-
-// Expiry: mark the IPs that keep a state, scan them into new dense ids (order
-// kept) and arena offsets, then build new tables from the survivors and swap.
-// The old tables are only read until the swap, so every failure before it
-// leaves the state as it was.
-extern "C" int bjx_state_expire(bjx_engine *e, int64_t cutoff_ns, bjx_expire_stats *out) {
-  if (!e) return BJX_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
-  hipEvent_t ev[4] = {};
-  struct EvFree {
-    hipEvent_t *ev;
-    ~EvFree() {
-      for (int k = 0; k < 4; ++k)
-        if (ev[k]) (void)hipEventDestroy(ev[k]);
-    }
-  } ev_free{ev};
-  try {
-    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_expire between bjx_match_batch and its bjx_finish_batch");
-    HIP_OK(hipSetDevice(e->device));
-    HIP_OK(hipDeviceSynchronize());  // nothing of an earlier batch may land after the rebuild
-    State &S = e->S;
-    hipStream_t st = e->stream;
-    for (auto &x : ev) HIP_OK(hipEventCreate(&x));
-    read_counters(e);
-    e->counters_fresh = false;
-    const uint64_t n_ips = e->host_counters[0], used = e->host_counters[1], n_st = e->host_counters[2];
-    if (n_ips >= 0x7FFFFFFFull) throw BjxError(BJX_ERR_CAPACITY, "more than 2^31 distinct IPs");
-    const uint64_t bytes_before = state_device_bytes(e->ip_cap, e->st_cap, S.arena_cap);
-
-    // mark, lengths, scans (temporaries only)
-    ExpAlloc tmp;
-    uint32_t *keep = tmp.get<uint32_t>(n_ips + 1), *nid = tmp.get<uint32_t>(n_ips + 1);
-    uint64_t *klen = tmp.get<uint64_t>(n_ips + 1), *noff = tmp.get<uint64_t>(n_ips + 1);
-    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_expire: no device memory for the scan buffers");
-    e->chk.ensure(8);
-    HIP_OK(hipEventRecord(ev[0], st));
-    HIP_OK(hipMemsetAsync(keep, 0, (n_ips + 1) * 4, st));
-    HIP_OK(hipMemsetAsync(e->chk.p, 0, 8, st));
-    hipLaunchKernelGGL(k_exp_mark, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st, e->st_cap,
-                       S.st, cutoff_ns, n_ips, keep, e->chk.p);
-    HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(k_exp_len, dim3(grid_for(n_ips + 1)), dim3(kBlock), 0, st, n_ips, keep, S.ip_len, klen);
-    HIP_OK(hipGetLastError());
-    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, keep, nid, (int)(n_ips + 1), st); });
-    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, klen, noff, (int)(n_ips + 1), st); });
-    HIP_OK(hipEventRecord(ev[1], st));
-    unsigned long long kept_st = 0;
-    uint32_t kept_ips32 = 0;
-    uint64_t kept_bytes = 0;
-    pin_get(e, &kept_st, e->chk.p, 8);
-    pin_get(e, &kept_ips32, nid + n_ips, 4);
-    pin_get(e, &kept_bytes, noff + n_ips, 8);
-    pin_sync(e);
-    const uint64_t kept_ips = kept_ips32;
-    if (kept_ips > n_ips || kept_bytes > used || kept_st > e->st_cap)
-      throw BjxError(BJX_ERR_DEVICE, "internal: expiry counts exceed the tables");
-
-    // the new tables: growth's sizing rule on the survivors, never below the
-    // capacity the engine was created with and never above the present one
-    const uint64_t ip_cap = std::min(e->ip_cap, std::max(e->ip_cap0, next_pow2(kept_ips * 4 / 3 + 1024)));
-    const uint64_t st_cap = std::min(e->st_cap, std::max(e->st_cap0, next_pow2(kept_st * 4 / 3 + 1024)));
-    const uint64_t arena_cap = std::min(S.arena_cap, std::max(e->arena_cap0, next_pow2(2 * kept_bytes + 4096)));
-    ExpAlloc nw;
-    IpSlot *n_ip = nw.get<IpSlot>(ip_cap);
-    uint32_t *n_first = nw.get<uint32_t>(ip_cap);
-    uint64_t *n_off = nw.get<uint64_t>(ip_cap);
-    uint32_t *n_len = nw.get<uint32_t>(ip_cap);
-    uint32_t *n_ipst = nw.get<uint32_t>(ip_cap);
-    uint8_t *n_arena = nw.get<uint8_t>(arena_cap);
-    StSlot *n_stt = nw.get<StSlot>(st_cap);
-    if (nw.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_expire: no device memory for the new tables (state unchanged)");
-    HIP_OK(hipEventRecord(ev[2], st));
-    HIP_OK(hipMemsetAsync(n_ip, 0, ip_cap * sizeof(IpSlot), st));
-    HIP_OK(hipMemsetAsync(n_first, 0xFF, ip_cap * 4, st));
-    HIP_OK(hipMemsetAsync(n_ipst, 0xFF, ip_cap * 4, st));
-    HIP_OK(hipMemsetAsync(n_stt, 0, st_cap * sizeof(StSlot), st));
-    if (n_ips) {
-      hipLaunchKernelGGL(k_exp_arena, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, keep, nid, noff, S.ip_off, S.ip_len,
-                         S.arena, used, n_arena, arena_cap, n_off, n_len);
-      HIP_OK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_exp_st, dim3(grid_for(e->st_cap)), dim3(kBlock), 0, st, e->st_cap, S.st, cutoff_ns, n_ips, nid, n_stt,
-                       st_cap - 1);
-    HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(k_exp_ip, dim3(grid_for(e->ip_cap)), dim3(kBlock), 0, st, e->ip_cap, S.ip, n_ips, keep, nid, n_ip,
-                       ip_cap - 1);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(ev[3], st));
-    HIP_OK(hipStreamSynchronize(st));
-
-    // swap; what is keyed by slot index or IP id starts over (ip_first, the
-    // ip_st slot cache: new and all ~0; sort2_hold as bjx_state_clear)
-    nw.take();
-    for (void *p : {(void *)S.ip, (void *)S.ip_first, (void *)S.ip_off, (void *)S.ip_len, (void *)S.ip_st, (void *)S.arena,
-                    (void *)S.st})
-      (void)hipFree(p);
-    S.ip = n_ip; S.ip_first = n_first; S.ip_off = n_off; S.ip_len = n_len; S.ip_st = n_ipst; S.arena = n_arena; S.st = n_stt;
-    S.ip_mask = ip_cap - 1;
-    S.st_mask = st_cap - 1;
-    S.arena_cap = arena_cap;
-    S.ip_st_cap = ip_cap;
-    if (st_cap > (1ull << 32)) S.hot_name = kNone;
-    else if (e->st_cap > (1ull << 32)) e->bound_uid = 0;  // back under 2^32 slots: the next batch re-binds and may cache again
-    e->ip_cap = ip_cap;
-    e->st_cap = st_cap;
-    e->sort2_hold = 0;
-    hipLaunchKernelGGL(k_exp_counters, dim3(1), dim3(64), 0, st, S.counters, kept_ips, kept_bytes, (uint64_t)kept_st);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(st));
-    e->host_counters[0] = kept_ips; e->host_counters[1] = kept_bytes; e->host_counters[2] = kept_st;
-    e->counters_fresh = false;  // the next stage reads them again
-    if (out) {
-      float a = 0, b = 0;
-      HIP_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-      HIP_OK(hipEventElapsedTime(&b, ev[2], ev[3]));
-      out->states_before = n_st; out->states_dropped = n_st - std::min<uint64_t>(n_st, kept_st);
-      out->ips_before = n_ips; out->ips_dropped = n_ips - kept_ips;
-      out->arena_bytes_before = used; out->arena_bytes_after = kept_bytes;
-      out->device_bytes_before = bytes_before;
-      out->device_bytes_after = state_device_bytes(ip_cap, st_cap, arena_cap);
-      out->device_ms = (double)a + (double)b;
-    }
-    return BJX_OK;
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return x.code;
-  } catch (const std::bad_alloc &) {
-    e->last_error = "host out of memory";
-    return BJX_ERR_NOMEM;
-  }
-}
-
-// ---- snapshot: bjx_state_export / bjx_state_import (format and host checks: snapshot.h)
-namespace {
-struct SnapEvents {
-  hipEvent_t ev[8] = {};
-  void create() {
-    for (auto &x : ev) HIP_OK(hipEventCreate(&x));
-  }
-  ~SnapEvents() {
-    for (auto &x : ev)
-      if (x) (void)hipEventDestroy(x);
-  }
-  double ms(int a, int b) {
-    float t = 0;
-    HIP_OK(hipEventElapsedTime(&t, ev[a], ev[b]));
-    return (double)t;
-  }
-};
-constexpr size_t kSnapChunk = 8u << 20;
-// device memory <-> the caller's in chunks through two pinned buffers, the copy
-// of one chunk running while the host moves the other
-void snap_copy_out(bjx_engine *e, uint8_t *dst, const uint8_t *d_src, uint64_t n) {
-  e->snap_pin.reserve(2 * kSnapChunk);
-  SnapEvents E;
-  E.create();
-  const uint64_t nc = (n + kSnapChunk - 1) / kSnapChunk;
-  auto land = [&](uint64_t c) {
-    HIP_OK(hipEventSynchronize(E.ev[c & 1]));
-    memcpy(dst + c * kSnapChunk, e->snap_pin.p + (c & 1) * kSnapChunk, (size_t)std::min<uint64_t>(kSnapChunk, n - c * kSnapChunk));
-  };
-  for (uint64_t c = 0; c < nc; ++c) {
-    HIP_OK(hipMemcpyAsync(e->snap_pin.p + (c & 1) * kSnapChunk, d_src + c * kSnapChunk,
-                          (size_t)std::min<uint64_t>(kSnapChunk, n - c * kSnapChunk), hipMemcpyDeviceToHost, e->stream));
-    HIP_OK(hipEventRecord(E.ev[c & 1], e->stream));
-    if (c) land(c - 1);
-  }
-  if (nc) land(nc - 1);
-}
-void snap_copy_in(bjx_engine *e, uint8_t *d_dst, const uint8_t *src, uint64_t n) {
-  e->snap_pin.reserve(2 * kSnapChunk);
-  SnapEvents E;
-  E.create();
-  const uint64_t nc = (n + kSnapChunk - 1) / kSnapChunk;
-  for (uint64_t c = 0; c < nc; ++c) {
-    const size_t m = (size_t)std::min<uint64_t>(kSnapChunk, n - c * kSnapChunk);
-    if (c >= 2) HIP_OK(hipEventSynchronize(E.ev[c & 1]));  // the chunk that used this buffer has left it
-    memcpy(e->snap_pin.p + (c & 1) * kSnapChunk, src + c * kSnapChunk, m);
-    HIP_OK(hipMemcpyAsync(d_dst + c * kSnapChunk, e->snap_pin.p + (c & 1) * kSnapChunk, m, hipMemcpyHostToDevice, e->stream));
-    HIP_OK(hipEventRecord(E.ev[c & 1], e->stream));
-  }
-  HIP_OK(hipStreamSynchronize(e->stream));
-}
-}  // namespace
-
-extern "C" uint64_t bjx_state_export_bound(bjx_engine *e) {
-  if (!e) return 0;
-  std::lock_guard<std::mutex> g(e->mu);
-  try {
-    HIP_OK(hipSetDevice(e->device));
-    read_counters(e);
-    uint64_t nb = 0;
-    for (auto &x : e->names) nb += x.size();
-    bjx_snap::Layout L;
-    const char *why = nullptr;
-    if (!bjx_snap::make_layout(e->names.size(), nb, e->host_counters[0], e->host_counters[1], e->host_counters[2], &L, &why)) {
-      e->last_error = std::string("bjx_state_export_bound: ") + why;
-      return 0;
-    }
-    return L.total;
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return 0;
-  }
-}
-
-// Export: expiry's mark / scan passes with min_start_ns as the cutoff, then
-// the records compacted, sorted by (ip, name) and written with the IP section
-// into one device buffer laid out as the snapshot's tail, which is copied out.
-// The tables are only read.
-extern "C" int bjx_state_export(bjx_engine *e, int64_t min_start_ns, uint8_t *out, uint64_t cap, uint64_t *len,
-                                bjx_snapshot_stats *stats) {
-  if (!e) return BJX_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
-  try {
-    if (len) *len = 0;
-    if (cap && !out) throw BjxError(BJX_ERR_ARG, "bjx_state_export: no output buffer");
-    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_export between bjx_match_batch and its bjx_finish_batch");
-    HIP_OK(hipSetDevice(e->device));
-    HIP_OK(hipDeviceSynchronize());
-    State &S = e->S;
-    hipStream_t st = e->stream;
-    SnapEvents E;
-    E.create();
-    read_counters(e);
-    const uint64_t n_ips = e->host_counters[0], used = e->host_counters[1], n_st = e->host_counters[2];
-    if (n_ips >= bjx_snap::kMaxIps) throw BjxError(BJX_ERR_CAPACITY, "bjx_state_export: 2^31 distinct IPs or more");
-    const uint32_t n_all = (uint32_t)e->names.size();
-
-    ExpAlloc tmp;
-    uint32_t *keep = tmp.get<uint32_t>(n_ips + 1), *nid = tmp.get<uint32_t>(n_ips + 1);
-    uint64_t *klen = tmp.get<uint64_t>(n_ips + 1), *noff = tmp.get<uint64_t>(n_ips + 1);
-    uint32_t *d_used = tmp.get<uint32_t>(n_all + 1), *d_remap = tmp.get<uint32_t>(n_all + 1);
-    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_export: no device memory for the scan buffers");
-    e->chk.ensure(8);
-    HIP_OK(hipEventRecord(E.ev[0], st));
-    HIP_OK(hipMemsetAsync(keep, 0, (n_ips + 1) * 4, st));
-    HIP_OK(hipMemsetAsync(d_used, 0, (n_all + 1) * 4, st));
-    HIP_OK(hipMemsetAsync(e->chk.p, 0, 16, st));
-    hipLaunchKernelGGL(k_exp_mark, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st, e->st_cap,
-                       S.st, min_start_ns, n_ips, keep, e->chk.p);
-    HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(k_exp_len, dim3(grid_for(n_ips + 1)), dim3(kBlock), 0, st, n_ips, keep, S.ip_len, klen);
-    HIP_OK(hipGetLastError());
-    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, keep, nid, (int)(n_ips + 1), st); });
-    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, klen, noff, (int)(n_ips + 1), st); });
-    HIP_OK(hipEventRecord(E.ev[1], st));
-    unsigned long long kept_st = 0;
-    uint32_t kept_ips32 = 0;
-    uint64_t kept_bytes = 0;
-    pin_get(e, &kept_st, e->chk.p, 8);
-    pin_get(e, &kept_ips32, nid + n_ips, 4);
-    pin_get(e, &kept_bytes, noff + n_ips, 8);
-    pin_sync(e);
-    const uint64_t kept_ips = kept_ips32;
-    if (kept_ips > n_ips || kept_bytes > used || kept_st > e->st_cap)
-      throw BjxError(BJX_ERR_DEVICE, "internal: export counts exceed the tables");
-    if (kept_st >= bjx_snap::kMaxStates) throw BjxError(BJX_ERR_CAPACITY, "bjx_state_export: 2^31 states or more");
-
-    // records, unsorted, with the engine's name ids; the names in use
-    uint64_t *keys = tmp.get<uint64_t>(kept_st), *keys2 = tmp.get<uint64_t>(kept_st);
-    uint32_t *idx = tmp.get<uint32_t>(kept_st), *idx2 = tmp.get<uint32_t>(kept_st);
-    int64_t *pay = tmp.get<int64_t>(2 * kept_st);
-    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_export: no device memory for the records");
-    HIP_OK(hipEventRecord(E.ev[2], st));
-    if (kept_st) {
-      hipLaunchKernelGGL(k_snap_compact, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st,
-                         e->st_cap, S.st, min_start_ns, n_ips, nid, n_all, d_used, e->chk.p + 1, (uint64_t)kept_st, keys, idx, pay);
-      HIP_OK(hipGetLastError());
-    }
-    HIP_OK(hipEventRecord(E.ev[3], st));
-    unsigned long long packed = 0;
-    std::vector<uint32_t> h_used(n_all + 1, 0);
-    pin_get(e, &packed, e->chk.p + 1, 8);
-    pin_sync(e);
-    HIP_OK(hipMemcpy(h_used.data(), d_used, (n_all + 1) * 4, hipMemcpyDeviceToHost));
-    if (packed != kept_st) throw BjxError(BJX_ERR_DEVICE, "internal: export passes disagree on the surviving states");
-
-    // canonical names: the used ones sorted bytewise; old id -> canonical index
-    std::vector<std::string> canon;
-    for (uint32_t k = 0; k < n_all; ++k)
-      if (h_used[k]) canon.push_back(e->names[k]);
-    std::sort(canon.begin(), canon.end());
-    std::vector<uint32_t> remap(n_all + 1, 0);
-    uint64_t names_bytes = 0;
-    for (auto &x : canon) names_bytes += x.size();
-    for (uint32_t k = 0; k < n_all; ++k)
-      if (h_used[k]) remap[k] = (uint32_t)(std::lower_bound(canon.begin(), canon.end(), e->names[k]) - canon.begin());
-    bjx_snap::Layout L;
-    const char *why = nullptr;
-    if (!bjx_snap::make_layout(canon.size(), names_bytes, kept_ips, kept_bytes, kept_st, &L, &why))
-      throw BjxError(BJX_ERR_CAPACITY, std::string("bjx_state_export: ") + why);
-    if (len) *len = L.total;
-    if (cap < L.total)
-      throw BjxError(BJX_ERR_CAPACITY, "bjx_state_export: the snapshot takes " + std::to_string(L.total) + " bytes, cap is " +
-                                           std::to_string(cap));
-
-    // the snapshot from ip_off on, built in device memory
-    const uint64_t body = L.total - L.o_ip_off;
-    uint8_t *d_body = tmp.get<uint8_t>(body + 16);
-    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_export: no device memory for the snapshot");
-    uint64_t *d_ipoff = reinterpret_cast<uint64_t *>(d_body);
-    uint8_t *d_ipb = d_body + (L.o_ips - L.o_ip_off);
-    uint64_t *d_recs = reinterpret_cast<uint64_t *>(d_body + (L.o_recs - L.o_ip_off));
-    HIP_OK(hipMemcpyAsync(d_remap, remap.data(), (n_all + 1) * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipEventRecord(E.ev[4], st));
-    HIP_OK(hipMemsetAsync(d_body, 0, L.o_recs - L.o_ip_off, st));  // the padding after the IP bytes
-    if (kept_st) {
-      hipLaunchKernelGGL(k_snap_remap, dim3(grid_for(kept_st)), dim3(kBlock), 0, st, (uint64_t)kept_st, keys, d_remap);
-      HIP_OK(hipGetLastError());
-      const int end_bit = 24 + std::max(1, bit_width(kept_ips));
-      cub_call(e, [&](void *t, size_t &b) {
-        return hipcub::DeviceRadixSort::SortPairs(t, b, keys, keys2, idx, idx2, (int)kept_st, 0, end_bit, st);
-      });
-      hipLaunchKernelGGL(k_snap_gather, dim3(grid_for(kept_st)), dim3(kBlock), 0, st, (uint64_t)kept_st, keys2, idx2, pay, d_recs);
-      HIP_OK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_snap_ips, dim3(grid_for(n_ips + 1)), dim3(kBlock), 0, st, n_ips, keep, nid, noff, S.ip_off, S.ip_len,
-                       S.arena, used, kept_ips, kept_bytes, d_ipoff, d_ipb);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(E.ev[5], st));
-    HIP_OK(hipStreamSynchronize(st));
-
-    bjx_snap::write_header(out, L);
-    bjx_snap::write_names(out, L, canon);
-    snap_copy_out(e, out + L.o_ip_off, d_body, body);
-    if (stats) {
-      stats->ips = kept_ips; stats->states = kept_st; stats->names = canon.size(); stats->bytes = L.total;
-      stats->ips_skipped = n_ips - kept_ips;
-      stats->states_skipped = n_st - std::min<uint64_t>(n_st, kept_st);
-      stats->device_ms = E.ms(0, 1) + E.ms(2, 3) + E.ms(4, 5);
-    }
-    return BJX_OK;
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return x.code;
-  } catch (const std::bad_alloc &) {
-    e->last_error = "host out of memory";
-    return BJX_ERR_NOMEM;
-  }
-}
-
-// Import into an empty engine: the snapshot's tail is uploaded and checked on
-// the device, the IPs this part owns are scanned into dense ids and arena
-// offsets, and new tables are built from them and swapped in.  Nothing of the
-// engine changes before the swap, so every failure leaves it empty.
-extern "C" int bjx_state_import(bjx_engine *e, const uint8_t *snap, uint64_t len, uint32_t part, uint32_t n_parts,
-                                bjx_snapshot_stats *stats) {
-  if (!e) return BJX_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
-  try {
-    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_import between bjx_match_batch and its bjx_finish_batch");
-    if (!snap) throw BjxError(BJX_ERR_ARG, "bjx_state_import: no snapshot");
-    if (n_parts < 1 || n_parts > kMaxParts || part >= n_parts)
-      throw BjxError(BJX_ERR_ARG, "bjx_state_import: part / n_parts out of range (n_parts 1..256, part < n_parts)");
-    HIP_OK(hipSetDevice(e->device));
-    HIP_OK(hipDeviceSynchronize());
-    State &S = e->S;
-    hipStream_t st = e->stream;
-    read_counters(e);
-    if (e->host_counters[0] || e->host_counters[2])
-      throw BjxError(BJX_ERR_ARG, "bjx_state_import: the engine holds state (import needs an empty engine)");
-    bjx_snap::Layout L;
-    std::vector<std::string> names;
-    if (const char *why = bjx_snap::validate_host(snap, len, &L, &names))
-      throw BjxError(BJX_ERR_ARG, std::string("bjx_state_import: ") + why);
-    const uint64_t n_ips = L.n_ips, n_states = L.n_states;
-    const uint32_t n_names = (uint32_t)L.n_names;
-    SnapEvents E;
-    E.create();
-
-    const uint64_t body = L.total - L.o_ip_off;
-    ExpAlloc tmp;
-    uint8_t *d_body = tmp.get<uint8_t>(body + 16);
-    uint32_t *keep = tmp.get<uint32_t>(n_ips + 1), *nid = tmp.get<uint32_t>(n_ips + 1);
-    uint64_t *klen = tmp.get<uint64_t>(n_ips + 1), *noff = tmp.get<uint64_t>(n_ips + 1), *hash = tmp.get<uint64_t>(n_ips + 1);
-    uint32_t *d_used = tmp.get<uint32_t>(n_names + 1), *d_remap = tmp.get<uint32_t>(n_names + 1), *d_err = tmp.get<uint32_t>(8);
-    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_import: no device memory for the snapshot");
-    const uint64_t *d_ipoff = reinterpret_cast<const uint64_t *>(d_body);
-    const uint8_t *d_ipb = d_body + (L.o_ips - L.o_ip_off);
-    const uint64_t *d_recs = reinterpret_cast<const uint64_t *>(d_body + (L.o_recs - L.o_ip_off));
-    snap_copy_in(e, d_body, snap + L.o_ip_off, body);
-
-    // the device checks: nothing else runs before they pass
-    HIP_OK(hipEventRecord(E.ev[0], st));
-    HIP_OK(hipMemsetAsync(d_err, 0, 32, st));
-    HIP_OK(hipMemsetAsync(d_used, 0, (n_names + 1) * 4, st));
-    hipLaunchKernelGGL(k_imp_check, dim3(grid_for(std::max(n_ips + 1, n_states))), dim3(kBlock), 0, st, n_ips, d_ipoff, L.ip_bytes,
-                       n_states, d_recs, n_names, d_used, d_err);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(E.ev[1], st));
-    uint32_t err[8] = {};
-    std::vector<uint32_t> h_used(n_names + 1, 0);
-    pin_get(e, err, d_err, 32);
-    pin_sync(e);
-    HIP_OK(hipMemcpy(h_used.data(), d_used, (n_names + 1) * 4, hipMemcpyDeviceToHost));
-    static const char *const kWhy[7] = {"", "ip_off: not monotone from 0", "ip_off: does not end at ip_bytes",
-                                        "records: ip index out of range", "records: name index out of range",
-                                        "records: not strictly ascending by (ip, name)", "records: an IP without a record"};
-    for (int c = 1; c < 7; ++c)
-      if (err[c]) throw BjxError(BJX_ERR_ARG, std::string("bjx_state_import: ") + kWhy[c]);
-    for (uint32_t k = 0; k < n_names; ++k)
-      if (!h_used[k]) throw BjxError(BJX_ERR_ARG, "bjx_state_import: names: a name no record uses");
-
-    // names into this engine's ids
-    std::vector<uint32_t> remap(n_names + 1, 0);
-    for (uint32_t k = 0; k < n_names; ++k) remap[k] = intern_name(e, names[k]);
-    HIP_OK(hipMemcpyAsync(d_remap, remap.data(), (n_names + 1) * 4, hipMemcpyHostToDevice, st));
-
-    // per IP: hash, owner filter; dense ids and arena offsets of the kept ones
-    e->chk.ensure(8);
-    HIP_OK(hipEventRecord(E.ev[2], st));
-    HIP_OK(hipMemsetAsync(e->chk.p, 0, 8, st));
-    hipLaunchKernelGGL(k_imp_ip, dim3(grid_for(n_ips + 1)), dim3(kBlock), 0, st, n_ips, d_ipoff, d_ipb, part, n_parts, keep, klen,
-                       hash);
-    HIP_OK(hipGetLastError());
-    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, keep, nid, (int)(n_ips + 1), st); });
-    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, klen, noff, (int)(n_ips + 1), st); });
-    if (n_states) {
-      hipLaunchKernelGGL(k_imp_count, dim3(grid_for(n_states)), dim3(kBlock), 0, st, n_states, d_recs, keep, e->chk.p);
-      HIP_OK(hipGetLastError());
-    }
-    HIP_OK(hipEventRecord(E.ev[3], st));
-    unsigned long long kept_st = 0;
-    uint32_t kept_ips32 = 0;
-    uint64_t kept_bytes = 0;
-    pin_get(e, &kept_st, e->chk.p, 8);
-    pin_get(e, &kept_ips32, nid + n_ips, 4);
-    pin_get(e, &kept_bytes, noff + n_ips, 8);
-    pin_sync(e);
-    const uint64_t kept_ips = kept_ips32;
-    if (kept_ips > n_ips || kept_bytes > L.ip_bytes || kept_st > n_states)
-      throw BjxError(BJX_ERR_DEVICE, "internal: import counts exceed the snapshot");
-
-    // the new tables: the growth rule on what this part keeps, never below the
-    // capacities the engine was created with; allocated before the old go
-    const uint64_t ip_cap = std::max(e->ip_cap0, next_pow2(kept_ips * 4 / 3 + 1024));
-    const uint64_t st_cap = std::max(e->st_cap0, next_pow2(kept_st * 4 / 3 + 1024));
-    const uint64_t arena_cap = std::max(e->arena_cap0, next_pow2(2 * kept_bytes + 4096));
-    ExpAlloc nw;
-    IpSlot *n_ip = nw.get<IpSlot>(ip_cap);
-    uint32_t *n_first = nw.get<uint32_t>(ip_cap);
-    uint64_t *n_off = nw.get<uint64_t>(ip_cap);
-    uint32_t *n_len = nw.get<uint32_t>(ip_cap);
-    uint32_t *n_ipst = nw.get<uint32_t>(ip_cap);
-    uint8_t *n_arena = nw.get<uint8_t>(arena_cap);
-    StSlot *n_stt = nw.get<StSlot>(st_cap);
-    if (nw.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_import: no device memory for the tables (the engine stays empty)");
-    // born: non-zero and below every later batch's epoch (run_batch counts up before it claims)
-    if (e->epoch == 0) e->epoch = 1;
-    const uint32_t born = e->epoch;
-    HIP_OK(hipEventRecord(E.ev[4], st));
-    HIP_OK(hipMemsetAsync(n_ip, 0, ip_cap * sizeof(IpSlot), st));
-    HIP_OK(hipMemsetAsync(n_first, 0xFF, ip_cap * 4, st));
-    HIP_OK(hipMemsetAsync(n_ipst, 0xFF, ip_cap * 4, st));
-    HIP_OK(hipMemsetAsync(n_stt, 0, st_cap * sizeof(StSlot), st));
-    if (n_ips) {
-      hipLaunchKernelGGL(k_imp_place, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, keep, nid, noff, hash, e->dbg_hash_mask,
-                         d_ipoff, d_ipb, born, kept_ips, n_arena, arena_cap, n_off, n_len, n_ip, ip_cap - 1);
-      HIP_OK(hipGetLastError());
-    }
-    if (n_states) {
-      hipLaunchKernelGGL(k_imp_st, dim3(grid_for(n_states)), dim3(kBlock), 0, st, n_states, d_recs, keep, nid, d_remap, n_stt,
-                         st_cap - 1);
-      HIP_OK(hipGetLastError());
-    }
-    if (n_ips) {
-      hipLaunchKernelGGL(k_imp_verify, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, keep, nid, hash, e->dbg_hash_mask,
-                         d_ipoff, d_ipb, kept_ips, n_ip, ip_cap - 1, n_off, n_len, n_arena, d_err);
-      HIP_OK(hipGetLastError());
-    }
-    HIP_OK(hipEventRecord(E.ev[5], st));
-    pin_get(e, err, d_err, 4);
-    pin_sync(e);
-    if (err[0]) throw BjxError(BJX_ERR_ARG, "bjx_state_import: ips: an IP appears twice in the snapshot");
-
-    // swap, as expiry does
-    nw.take();
-    for (void *p : {(void *)S.ip, (void *)S.ip_first, (void *)S.ip_off, (void *)S.ip_len, (void *)S.ip_st, (void *)S.arena,
-                    (void *)S.st})
-      (void)hipFree(p);
-    S.ip = n_ip; S.ip_first = n_first; S.ip_off = n_off; S.ip_len = n_len; S.ip_st = n_ipst; S.arena = n_arena; S.st = n_stt;
-    S.ip_mask = ip_cap - 1;
-    S.st_mask = st_cap - 1;
-    S.arena_cap = arena_cap;
-    S.ip_st_cap = ip_cap;
-    if (st_cap > (1ull << 32)) S.hot_name = kNone;
-    else if (e->st_cap > (1ull << 32)) e->bound_uid = 0;
-    e->ip_cap = ip_cap;
-    e->st_cap = st_cap;
-    e->sort2_hold = 0;
-    hipLaunchKernelGGL(k_exp_counters, dim3(1), dim3(64), 0, st, S.counters, kept_ips, kept_bytes, (uint64_t)kept_st);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(st));
-    e->host_counters[0] = kept_ips; e->host_counters[1] = kept_bytes; e->host_counters[2] = kept_st;
-    e->counters_fresh = false;
-    if (stats) {
-      stats->ips = kept_ips; stats->states = kept_st; stats->names = n_names; stats->bytes = len;
-      stats->ips_skipped = n_ips - kept_ips;
-      stats->states_skipped = n_states - kept_st;
-      stats->device_ms = E.ms(0, 1) + E.ms(2, 3) + E.ms(4, 5);
-    }
-    return BJX_OK;
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return x.code;
-  } catch (const std::bad_alloc &) {
-    e->last_error = "host out of memory";
-    return BJX_ERR_NOMEM;
-  }
-}
-
-// ---- query: bjx_state_query (filter checks, sort key, name ranks: state_query.h)
-namespace {
-// the radix select stops at this many candidates for `need` rows still
-// wanted: what is left is sorted, so the sort stays O(limit)
-inline uint64_t qry_small(uint64_t need) { return 2 * need + 256; }
-}  // namespace
-
-// Query: one pass over the state table (or one probe per interned name of one
-// IP) counts the passing states and appends them as 16-byte candidates; a
-// radix select narrows them to the wanted rows plus a remainder of O(limit),
-// which is sorted; the rows and their bytes are gathered on the device and
-// copied out.  The tables are only read.  The candidate buffer is sized by the
-// `states` counter (the most a scan can append).
-extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_state_rows *out) {
-  if (!e || !f || !out) return BJX_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
-  try {
-    memset(out, 0, sizeof *out);
-    if (const char *why = bjx_query::check_filter(f)) throw BjxError(BJX_ERR_ARG, std::string("bjx_state_query: ") + why);
-    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_query between bjx_match_batch and its bjx_finish_batch");
-    HIP_OK(hipSetDevice(e->device));
-    HIP_OK(hipDeviceSynchronize());
-    State &S = e->S;
-    hipStream_t st = e->stream;
-    SnapEvents E;
-    E.create();
-    read_counters(e);
-    const uint64_t n_ips = e->host_counters[0], used = e->host_counters[1], n_st = e->host_counters[2];
-    const uint32_t n_names = (uint32_t)e->names.size();
-    e->qry_rows.clear();
-    e->qry_bytes.clear();
-    QFilter F{f->min_hits, f->min_start_ns, f->max_start_ns, kNone, f->order == BJX_QUERY_BY_START ? 1u : 0u};
-    if (f->name.ptr) {
-      auto it = e->name_ids.find(std::string(f->name.ptr, f->name.len));
-      if (it == e->name_ids.end()) return BJX_OK;  // never interned: no state can carry it
-      F.name = it->second;
-    }
-    if (bjx_query::empty_window(*f) || !n_ips || !n_st || !n_names) return BJX_OK;
-    if (n_ips >= bjx_snap::kMaxIps) throw BjxError(BJX_ERR_CAPACITY, "bjx_state_query: 2^31 distinct IPs or more");
-    const bool by_ip = f->ip.ptr != nullptr;
-    const uint64_t limit = f->limit;
-    const uint64_t room = limit ? (by_ip ? (uint64_t)n_names : n_st) : 0;
-    const uint64_t rows_max = std::min(limit, room);
-    const uint64_t fin_cap = rows_max ? rows_max + qry_small(rows_max) : 0;
-
-    // name ranks (tie word), rank -> id and the name bytes in rank order (the rows' names)
-    std::vector<uint32_t> rank, by_rank;
-    bjx_query::name_ranks(e->names, &rank, &by_rank);
-    std::vector<uint64_t> noff(n_names + 1, 0);
-    std::string nbytes;
-    for (uint32_t r = 0; r < n_names; ++r) {
-      noff[r] = nbytes.size();
-      nbytes += e->names[by_rank[r]];
-    }
-    noff[n_names] = nbytes.size();
-
-    // every buffer whose size is known now, before anything is launched
-    ExpAlloc tmp;
-    uint32_t *keep = by_ip ? nullptr : tmp.get<uint32_t>(n_ips + 1);
-    uint32_t *d_sum = tmp.get<uint32_t>(4);
-    uint32_t *d_rank = tmp.get<uint32_t>(n_names), *d_by_rank = tmp.get<uint32_t>(n_names);
-    uint64_t *d_noff = tmp.get<uint64_t>(n_names + 1);
-    uint8_t *d_nbytes = tmp.get<uint8_t>(nbytes.size() + 16);
-    unsigned long long *d_ctr = tmp.get<unsigned long long>(4 + 256);  // [0] matched [1] appended [2] selected [3] next set; the histogram
-    ulonglong2 *cand = tmp.get<ulonglong2>(room), *fin = tmp.get<ulonglong2>(fin_cap);
-    uint64_t *k0 = tmp.get<uint64_t>(fin_cap), *k1 = tmp.get<uint64_t>(fin_cap);
-    uint32_t *i0 = tmp.get<uint32_t>(fin_cap), *i1 = tmp.get<uint32_t>(fin_cap);
-    bjx_state_row *d_rows = tmp.get<bjx_state_row>(rows_max);
-    uint64_t *d_lens = tmp.get<uint64_t>(rows_max + 1), *d_offs = tmp.get<uint64_t>(rows_max + 1);
-    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_query: no device memory for the candidates");
-    HIP_OK(hipMemcpyAsync(d_rank, rank.data(), n_names * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_by_rank, by_rank.data(), n_names * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_noff, noff.data(), (n_names + 1) * 8, hipMemcpyHostToDevice, st));
-    if (!nbytes.empty()) HIP_OK(hipMemcpyAsync(d_nbytes, nbytes.data(), nbytes.size(), hipMemcpyHostToDevice, st));
-    uint64_t h = 0;
-    if (by_ip) {
-      e->q_ip.ensure(f->ip.len + 1);
-      if (f->ip.len) HIP_OK(hipMemcpyAsync(e->q_ip.p, f->ip.ptr, f->ip.len, hipMemcpyHostToDevice, st));
-      h = hash_bytes(reinterpret_cast<const uint8_t *>(f->ip.ptr), (uint32_t)f->ip.len);
-      if (e->dbg_hash_mask) h = (h & e->dbg_hash_mask) | 1;
-    }
-    HIP_OK(hipStreamSynchronize(st));  // the uploads read host vectors
-    double ms = 0;
-
-    // 1. the passing states: counts, keep[], candidates
-    HIP_OK(hipEventRecord(E.ev[0], st));
-    HIP_OK(hipMemsetAsync(d_ctr, 0, (4 + 256) * 8, st));
-    HIP_OK(hipMemsetAsync(d_sum, 0, 16, st));
-    if (by_ip) {
-      hipLaunchKernelGGL(k_qry_ip, dim3((unsigned)std::min<uint64_t>(grid_for(n_names), 1024)), dim3(kBlock), 0, st, S, h,
-                         e->q_ip.p, (uint32_t)f->ip.len, F, n_ips, n_names, d_rank, d_ctr, room, cand);
-      HIP_OK(hipGetLastError());
-    } else {
-      HIP_OK(hipMemsetAsync(keep, 0, (n_ips + 1) * 4, st));
-      hipLaunchKernelGGL(k_qry_scan, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st, e->st_cap,
-                         S.st, F, n_ips, n_names, d_rank, keep, d_ctr, room, cand);
-      HIP_OK(hipGetLastError());
-      cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceReduce::Sum(t, b, keep, d_sum, (int)n_ips, st); });
-    }
-    HIP_OK(hipEventRecord(E.ev[1], st));
-    unsigned long long got[2] = {0, 0};
-    uint32_t ips_matched = 0;
-    pin_get(e, got, d_ctr, 16);
-    pin_get(e, &ips_matched, d_sum, 4);
-    pin_sync(e);
-    ms += E.ms(0, 1);
-    const uint64_t matched = got[0];
-    if (matched > n_st || (room && got[1] != matched))
-      throw BjxError(BJX_ERR_DEVICE, "internal: query counts disagree with the tables");
-    out->n_matched = matched;
-    out->n_ips_matched = by_ip ? (matched ? 1 : 0) : ips_matched;
-    const uint64_t n_rows = std::min(limit, matched);
-    if (!n_rows) {
-      out->device_ms = ms;
-      return BJX_OK;
-    }
-
-    // 2. radix select, most significant byte first: through the primary word
-    // into the tie word while the bucket the limit falls into is still large
-    ulonglong2 *cur = cand, *spare = nullptr;
-    uint64_t n_cur = matched, n_sel = 0, spare_cap = 0;
-    for (int pass = 0; pass < 16 && n_cur > qry_small(n_rows - n_sel); ++pass) {
-      const uint32_t word = pass < 8 ? 0u : 1u, shift = 56u - 8u * (uint32_t)(pass & 7);
-      const uint64_t need = n_rows - n_sel;
-      const unsigned grid = (unsigned)std::min<uint64_t>(grid_for(n_cur), 4096);
-      HIP_OK(hipEventRecord(E.ev[0], st));
-      HIP_OK(hipMemsetAsync(d_ctr + 4, 0, 256 * 8, st));
-      hipLaunchKernelGGL(k_qry_hist, dim3(grid), dim3(kBlock), 0, st, cur, n_cur, word, shift, d_ctr + 4);
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipEventRecord(E.ev[1], st));
-      unsigned long long hist[256];
-      pin_get(e, hist, d_ctr + 4, sizeof hist);
-      pin_sync(e);
-      ms += E.ms(0, 1);
-      uint64_t below = 0;
-      uint32_t b = 0;
-      for (; b < 256 && below + hist[b] < need; ++b) below += hist[b];
-      if (b == 256) throw BjxError(BJX_ERR_DEVICE, "internal: query histogram does not add up");
-      const uint64_t in_b = hist[b];
-      if (in_b == n_cur) continue;  // every candidate has this digit: nothing to move
-      ulonglong2 *nxt;
-      if (cur == cand) {
-        if (!spare) {
-          spare = tmp.get<ulonglong2>(in_b);
-          spare_cap = in_b;
-          if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_query: no device memory for the selection");
-        }
-        nxt = spare;
-      } else {
-        nxt = cand;
-      }
-      const uint64_t nxt_cap = nxt == cand ? room : spare_cap;
-      if (in_b > nxt_cap || n_sel + below > fin_cap) throw BjxError(BJX_ERR_DEVICE, "internal: query selection exceeds its buffers");
-      HIP_OK(hipEventRecord(E.ev[0], st));
-      HIP_OK(hipMemsetAsync(d_ctr + 3, 0, 8, st));
-      hipLaunchKernelGGL(k_qry_filter, dim3(grid), dim3(kBlock), 0, st, cur, n_cur, word, shift, b, fin, fin_cap, nxt, nxt_cap,
-                         d_ctr + 2);
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipEventRecord(E.ev[1], st));
-      unsigned long long moved[2] = {0, 0};
-      pin_get(e, moved, d_ctr + 2, 16);
-      pin_sync(e);
-      ms += E.ms(0, 1);
-      if (moved[0] != n_sel + below || moved[1] != in_b)
-        throw BjxError(BJX_ERR_DEVICE, "internal: query selection disagrees with its histogram");
-      n_sel += below;
-      n_cur = in_b;
-      cur = nxt;
-    }
-    const uint64_t m = n_sel + n_cur;
-    if (m > fin_cap || m < n_rows) throw BjxError(BJX_ERR_DEVICE, "internal: query selection did not converge");
-
-    // 3. sort the selected and the remainder by (primary, tie): two stable
-    // sorts through an index, the tie word first; gather the rows
-    HIP_OK(hipEventRecord(E.ev[0], st));
-    HIP_OK(hipMemcpyAsync(fin + n_sel, cur, n_cur * sizeof(ulonglong2), hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_qry_split, dim3(grid_for(m)), dim3(kBlock), 0, st, m, fin, k0, i0);
-    HIP_OK(hipGetLastError());
-    const int tie_bits = std::min(64, 24 + std::max(1, bit_width(n_ips)));
-    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0, k1, i0, i1, (int)m, 0, tie_bits, st); });
-    hipLaunchKernelGGL(k_qry_prim, dim3(grid_for(m)), dim3(kBlock), 0, st, m, fin, i1, k0);
-    HIP_OK(hipGetLastError());
-    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0, k1, i1, i0, (int)m, 0, 64, st); });
-    hipLaunchKernelGGL(k_qry_rows, dim3(grid_for(n_rows + 1)), dim3(kBlock), 0, st, n_rows, m, fin, i0, S, n_ips, n_names, d_by_rank,
-                       d_noff, d_rows, d_lens);
-    HIP_OK(hipGetLastError());
-    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, d_lens, d_offs, (int)(n_rows + 1), st); });
-    HIP_OK(hipEventRecord(E.ev[1], st));
-    uint64_t total = 0;
-    pin_get(e, &total, d_offs + n_rows, 8);
-    pin_sync(e);
-    ms += E.ms(0, 1);
-    uint8_t *d_bytes = tmp.get<uint8_t>(total + 16);
-    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_query: no device memory for the rows' bytes");
-    HIP_OK(hipEventRecord(E.ev[0], st));
-    hipLaunchKernelGGL(k_qry_bytes, dim3(grid_for(n_rows)), dim3(kBlock), 0, st, n_rows, m, fin, i0, S, n_ips, used, d_noff, d_nbytes,
-                       d_offs, total, d_rows, d_bytes);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(E.ev[1], st));
-    e->qry_rows.resize(n_rows);
-    e->qry_bytes.resize(total + 1);
-    HIP_OK(hipMemcpyAsync(e->qry_rows.data(), d_rows, n_rows * sizeof(bjx_state_row), hipMemcpyDeviceToHost, st));
-    if (total) HIP_OK(hipMemcpyAsync(e->qry_bytes.data(), d_bytes, total, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    ms += E.ms(0, 1);
-    out->n_rows = n_rows;
-    out->rows = e->qry_rows.data();
-    out->bytes = e->qry_bytes.data();
-    out->n_bytes = total;
-    out->device_ms = ms;
-    return BJX_OK;
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return x.code;
-  } catch (const std::bad_alloc &) {
-    e->last_error = "host out of memory";
-    return BJX_ERR_NOMEM;
-  }
-}
-
-extern "C" size_t bjx_state_dump(bjx_engine *e, char *out, size_t cap) {
-  if (!e) return 0;
-  std::lock_guard<std::mutex> g(e->mu);
-  try {
-    HIP_OK(hipSetDevice(e->device));
-    read_counters(e);
-    const uint64_t n_ips = e->host_counters[0], used = e->host_counters[1];
-    std::vector<uint64_t> off(n_ips);
-    std::vector<uint32_t> len(n_ips);
-    std::vector<StSlot> st(e->st_cap);
-    std::vector<uint8_t> arena(used);
-    HIP_OK(hipMemcpy(off.data(), e->S.ip_off, n_ips * 8, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(len.data(), e->S.ip_len, n_ips * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(arena.data(), e->S.arena, used, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(st.data(), e->S.st, e->st_cap * sizeof(StSlot), hipMemcpyDeviceToHost));
-    std::vector<std::vector<std::pair<uint32_t, uint64_t>>> per_ip(n_ips);
-    for (uint64_t i = 0; i < e->st_cap; ++i)
-      if (st[i].key && st[i].valid) per_ip[(st[i].key >> 24) - 1].push_back({(uint32_t)(st[i].key & 0xFFFFFF), i});
-    std::string s;
-    char buf[96];
-    for (uint64_t id = 0; id < n_ips; ++id) {
-      s.append(reinterpret_cast<const char *>(arena.data() + off[id]), len[id]);
-      s += ":\n";
-      std::sort(per_ip[id].begin(), per_ip[id].end(),
-                [&](const std::pair<uint32_t, uint64_t> &a, const std::pair<uint32_t, uint64_t> &b) {
-                  return e->names[a.first] < e->names[b.first];
-                });
-      for (auto &p : per_ip[id]) {
-        s += "\t" + e->names[p.first] + ":\n";
-        snprintf(buf, sizeof buf, "\t\t{%lld %lld}\n", (long long)st[p.second].hits, (long long)st[p.second].start);
-        s += buf;
-      }
-      s += "\n";
-    }
-    if (out && cap) memcpy(out, s.data(), std::min(cap, s.size()));
-    return s.size();
-  } catch (const BjxError &x) {
-    e->last_error = x.what();
-    return 0;
-  }
 }
 
 // ------------------------------------------------------------ self-test hooks
