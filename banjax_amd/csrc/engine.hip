@@ -533,7 +533,10 @@ __device__ void parse_and_match(const Bind &B, const uint8_t *__restrict__ p, ui
     ++pos;
     if ((pos & 63) == 0) { L.mword(j, wi++) = word; word = 0; }
   }
-  if (pos & 63) L.mword(j, wi) = word;
+  if (pos & 63) L.mword(j, wi++) = word;
+  // the words past this scope (the ruleset's widest scope sets mask_words): no
+  // reader needs them, but BJX_CHECK's k_check_masks counts all of a line's words
+  for (; wi < B.mask_words; ++wi) L.mword(j, wi) = 0;
   L.counts[j] = ((uint64_t)nres << 32) | nev;
 }
 
@@ -3007,9 +3010,14 @@ __global__ __launch_bounds__(kBlock) void k_nfa_wide(Bind B, const uint8_t *__re
       m = s_flag != 0;
     }
     if (m && tid == 0) {
+      // the event is counted for the line's own rule at pos, as k_emit resolves
+      // it: r is the pattern's first rule, whose hosts_to_skip may differ
       const int32_t hid = L.host_id[j];
+      uint32_t s_begin = 0, s_end = 0;
+      if (hid >= 0) { s_begin = B.site_off[hid]; s_end = B.site_off[hid + 1]; }
+      const uint32_t own = pos < s_end - s_begin ? B.site_rules[s_begin + pos] : B.global_rules[pos - (s_end - s_begin)];
       atomicOr(reinterpret_cast<unsigned long long *>(&L.mword(j, pos >> 6)), 1ull << (pos & 63));
-      atomicAdd(reinterpret_cast<unsigned long long *>(L.counts + j), (1ull << 32) | (is_skip(B, r, hid) ? 0ull : 1ull));
+      atomicAdd(reinterpret_cast<unsigned long long *>(L.counts + j), (1ull << 32) | (is_skip(B, own, hid) ? 0ull : 1ull));
     }
     wide_sync<GLB>();  // the next job reuses A / Yb / gmark / s_flag
   }

@@ -157,6 +157,19 @@ def test_wide_rules_match_oracle(engine):
     pair.compare_state(["10.0.1.1", "10.0.3.7"])
 
 
+def test_wide_rules_sharing_a_pattern_differ_in_hosts_to_skip(engine):
+    """Two rules with one wide pattern: the line kernel's job names the first; the event is
+    counted for the rule at the job's position (hosts_to_skip in either order, k_emit's view)."""
+    skip = "\n    hosts_to_skip:\n      h0.com: true"
+    rule = "  - rule: 'w%d'\n    regex: 'a.{750}.{750}b'\n    interval: 5\n    hits_per_interval: 1\n    decision: challenge%s\n"
+    line = b"1700000000.%03d 10.0.0.%d GET h%d.com GET /" + b"a" + b"." * 1500 + b"b\n"
+    for order in ((0, 1, 0), (1, 0, 1)):
+        pair = Pair("regexes_with_rates:\n" + "".join(rule % (k, skip if s else "") for k, s in enumerate(order)), engine)
+        out = pair.feed(b"".join(line % (j, j % 2, j % 2) for j in range(3)), 1700000000 * S)
+        assert out.n_results == 9 and out.n_events == 9 - 2 * sum(order)  # two of the three lines are h0.com's
+        pair.compare_state(["10.0.0.0", "10.0.0.1"])
+
+
 def test_forced_wide_edge_lines_and_corpus(engine, forced_wide):
     """Every edge-case rule (\\b, ^ / $, (?i) folds, negated classes, Unicode
     groups) through k_nfa_wide: its sparse group and assertion target lists."""
