@@ -551,21 +551,19 @@ BJX_HDN int go_parse_float(const uint8_t *s, uint32_t n, double *out, Decimal *d
     return rc;
   }
   // decimal: exact multi-precision conversion of the digit string
-  dec->nd = 0; dec->dp = 0; dec->neg = neg; dec->trunc = false;
-  {
-    bool sd = false;
-    for (uint32_t k = digits_begin; k < mant_end; ++k) {
-      uint8_t c = s[k];
-      if (c == '_') continue;
-      if (c == '.') { sd = true; dec->dp = dec->nd; continue; }
-      if (c == '0' && dec->nd == 0) { dec->dp--; continue; }
-      if (dec->nd < 800) dec->d[dec->nd++] = (uint8_t)(c - '0');
-      else if (c != '0') dec->trunc = true;
-    }
-    if (!sd) dec->dp = dec->nd;
-    dec->dp += eexp;
-    dec_trim(dec);
+  // The decimal point comes from readFloat's count of every digit (dp above),
+  // not from the digits kept: with more than 800 digits before the point the
+  // kept count would place it 800 digits in and lose the rest of the magnitude
+  // ("1" + 1200 zeros + "e-1191" is 1e9; Go returns that from its fast path).
+  dec->nd = 0; dec->dp = dp; dec->neg = neg; dec->trunc = false;
+  for (uint32_t k = digits_begin; k < mant_end; ++k) {
+    uint8_t c = s[k];
+    if (c == '_' || c == '.') continue;
+    if (c == '0' && dec->nd == 0) continue;
+    if (dec->nd < 800) dec->d[dec->nd++] = (uint8_t)(c - '0');
+    else if (c != '0') dec->trunc = true;
   }
+  dec_trim(dec);
   bool ovf;
   uint64_t bits = dec_float_bits(dec, &ovf);
   *out = bits_to_double(bits);

@@ -2,6 +2,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "allow_entry.h"
+
 namespace bjx {
 
 // One compiled rule as the kernels see it (rule tables live in one blob).
@@ -74,12 +76,7 @@ __host__ __device__ inline uint32_t gram_slot(uint32_t g, uint32_t cap) { return
 constexpr int kCandSlots = 4;  // literal hits kept per line (more = overflow: every literal rule by DFA)
 constexpr uint64_t kCandVerified = 1u << 23;  // hit bytes already checked by the scan pass
 
-struct Subnet {
-  uint8_t net[16];
-  uint8_t mask[16];
-  uint32_t netlen;  // 4 (IPv4 compare, To4 semantics) or 16
-  uint32_t _pad;
-};
+// struct Subnet (the allow-list subnets of Bind::sc_sub): allow_entry.h, with the host code that fills it
 
 struct ImgLayout {
   uint32_t gt, ge, ht, hrec, hid, hbytes, lrec, lbytes, lcim, lchk;
