@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("BJX_LIB_PATH") or os.path.join(HERE, "lib", "libbanja
 OK = 0
 ERR_REGEX, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_TOO_COMPLEX, ERR_CAPACITY, ERR_DECISION = -1, -2, -3, -4, -5, -6, -7
 TAIL_STOPPED, ERR_IO = -8, -9
-INPUT_DEVICE, COPY_RESULTS, EMIT_BANS, BAN_RECORDS_ONLY, TRIPS_COMPACT = 1, 2, 4, 8, 16
+INPUT_DEVICE, COPY_RESULTS, EMIT_BANS, BAN_RECORDS_ONLY, TRIPS_COMPACT, RULE_STATS = 1, 2, 4, 8, 16, 32
 
 
 class Str(C.Structure):
@@ -111,6 +111,8 @@ EXPORTS = [
     "bjx_state_export_bound", "bjx_state_export", "bjx_state_import",
     "bjx_node_state_export_bound", "bjx_node_state_export", "bjx_node_state_import",
     "bjx_state_query", "bjx_node_state_query",
+    "bjx_batch_rule_stats", "bjx_rule_stats_total", "bjx_rule_stats_reset",
+    "bjx_node_batch_rule_stats", "bjx_node_rule_stats_total", "bjx_node_rule_stats_reset",
 ]
 
 
@@ -152,6 +154,17 @@ class StateRows(C.Structure):
     _fields_ = [("n_matched", C.c_uint64), ("n_ips_matched", C.c_uint64), ("n_rows", C.c_uint64),
                 ("rows", C.POINTER(StateRow)), ("bytes", C.c_void_p), ("n_bytes", C.c_uint64),
                 ("device_ms", C.c_double)]
+
+
+class RuleStat(C.Structure):
+    """bjx_rule_stat: one rule's RuleResults of the batches counted (24 B)."""
+    _fields_ = [("matches", C.c_uint64), ("skip_host", C.c_uint64), ("trips", C.c_uint64)]
+
+
+class RuleStats(C.Structure):
+    """bjx_rule_stats: the per-rule rows of the last batch or of every flagged batch."""
+    _fields_ = [("n_rules", C.c_uint64), ("rules", C.POINTER(RuleStat)), ("n_batches", C.c_uint64),
+                ("n_lines", C.c_uint64), ("device_ms", C.c_double)]
 
 
 _lib = None
@@ -309,6 +322,16 @@ def lib():
     for name in ("bjx_state_query", "bjx_node_state_query"):
         f = getattr(L, name)
         f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(StateRows)]
+    for pre in ("bjx_", "bjx_node_"):
+        for name in ("batch_rule_stats", "rule_stats_total"):
+            f = getattr(L, pre + name)
+            f.restype, f.argtypes = C.c_int, [vp, C.POINTER(RuleStats)]
+        f = getattr(L, pre + "rule_stats_reset")
+        f.restype, f.argtypes = C.c_int, [vp]
+    L.bjx_debug_set_rule_stats_lds.restype = C.c_int
+    L.bjx_debug_set_rule_stats_lds.argtypes = [vp, C.c_uint32]
+    L.bjx_debug_rule_stats_path.restype = C.c_int
+    L.bjx_debug_rule_stats_path.argtypes = [vp]
     _lib = L
     return L
 

@@ -5037,6 +5037,9 @@ extern "C" int bjx_ruleset_compile(const bjx_rule_spec *global_rules, size_t n_g
 
 extern "C" void bjx_ruleset_release(bjx_ruleset *rs) { delete rs; }
 extern "C" size_t bjx_ruleset_num_rules(const bjx_ruleset *rs) { return rs ? rs->rules.size() : 0; }
+// Library-internal (node.cpp; not in the public header): the serial number a
+// ruleset got when it was compiled, which no later ruleset repeats.
+extern "C" uint64_t bjx_internal_ruleset_serial(const bjx_ruleset *rs) { return rs ? rs->uid : 0; }
 extern "C" int bjx_ruleset_rule_info(const bjx_ruleset *rs, size_t i, uint32_t *states, uint32_t *classes, uint32_t *flags) {
   if (!rs || i >= rs->rules.size()) return BJX_ERR_ARG;
   const auto &rx = rs->rules[i].rx;
@@ -5058,6 +5061,8 @@ struct BatchCtx {
   int64_t now_ns = 0;
   Lines L{};
   bool live = false;
+  uint64_t rs_uid = 0;    // the batch's ruleset: its serial number and rule count (set even when not live)
+  uint32_t rs_rules = 0;
 };
 
 struct bjx_engine {
@@ -5227,6 +5232,20 @@ struct bjx_engine {
   HostBuf<uint8_t> snap_pin;  // bjx_state_export / bjx_state_import: two pinned chunks the blob moves through
   HostBuf<bjx_state_row> qry_rows;  // bjx_state_query: the last answer (valid until the next query)
   HostBuf<uint8_t> qry_bytes;
+
+  // per-rule counts of the batches closed with BJX_RULE_STATS (rule_stats.h);
+  // nothing here is allocated or created before the first such batch
+  DevBuf<unsigned long long> rs_cnt;  // matches, skip_host, trips: three planes of n_rules counters
+  HostBuf<uint64_t> rs_pin;           // their host copy
+  hipEvent_t rs_ev[2] = {};           // around the counting alone
+  uint32_t rs_lds_rules = 0;          // bjx_debug_set_rule_stats_lds (0 = default)
+  uint32_t rs_lds_set = 0;            // dynamic LDS k_rule_hist was last raised to (rulesets past 8,192 rules)
+  bool rs_counted = false;            // the last batch was closed with the flag (and its check passed)
+  std::vector<bjx_rule_stat> rs_last, rs_total;
+  uint32_t rs_path = 0;               // where the last flagged batch binned: 1 LDS, 2 global counters, 0 nothing launched
+  uint64_t rs_uid = 0;                // ruleset serial of the totals (0: no flagged batch since creation / reset)
+  uint64_t rs_last_lines = 0, rs_batches = 0, rs_lines = 0;
+  double rs_last_ms = 0, rs_ms = 0;
 };
 
 namespace {
@@ -6746,6 +6765,8 @@ extern "C" void bjx_engine_destroy(bjx_engine *e) {
   e->snap_pin.release();
   e->qry_rows.release();
   e->qry_bytes.release();
+  e->rs_cnt.release(); e->rs_pin.release();
+  for (auto &x : e->rs_ev) if (x) (void)hipEventDestroy(x);
   e->l_ip16.release(); e->jline.release(); e->jkey.release(); e->jidx.release(); e->jidx2.release(); e->jrec.release(); e->jkey2.release(); e->l_cand.release(); e->l_ccnt.release(); e->l_cfirst.release();
   (void)hipEventDestroy(e->ev0); (void)hipEventDestroy(e->ev1); (void)hipEventDestroy(e->evm0); (void)hipEventDestroy(e->evm1);
   for (auto &x : e->evk) (void)hipEventDestroy(x);
@@ -7207,6 +7228,9 @@ static void run_nfa_jobs(bjx_engine *e, const Bind &B, const uint8_t *buf, uint6
 static bool match_phase(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *bytes, size_t n, int64_t now_ns, uint32_t flags,
                         bjx_batch_result *out) {
   e->bc = BatchCtx{};
+  e->bc.rs_uid = rs->uid;
+  e->bc.rs_rules = (uint32_t)rs->rules.size();
+  e->rs_counted = false;
   HIP_OK(hipSetDevice(e->device));
   if (e->bound_uid != rs->uid || e->bound_dec_version != e->decisions_version) {
     // (re)binding: calibrate the gram filter on the head of this batch
@@ -7795,6 +7819,9 @@ static void emit_bans(bjx_engine *e, uint64_t n, bool records_only) {
   e->ban_n_trips = n;
 }
 
+// per-rule counts of a batch closed with BJX_RULE_STATS
+#include "rule_stats.h"
+
 // Where finish_phase finds the trips: Apply outcomes in state-slot order (this
 // engine's rate-limit stage), outcomes in event order (a node's
 // bjx_finish_batch), or a list of the tripping events (bjx_finish_batch_trips)
@@ -7912,6 +7939,10 @@ static void finish_phase(bjx_engine *e, uint32_t flags, bjx_batch_result *out, F
       }
     }
   }
+  // per-rule counts: the masks and counts are still current, the trips built
+  const bool rule_stats = (flags & BJX_RULE_STATS) != 0;
+  e->rs_counted = false;
+  if (rule_stats && n_res) rule_stats_launch(e, n_trips);
   HIP_OK(hipEventRecord(e->ev1, st));
   mark(e, 8);
   if (flags & BJX_COPY_RESULTS) {
@@ -7927,6 +7958,7 @@ static void finish_phase(bjx_engine *e, uint32_t flags, bjx_batch_result *out, F
     }
   }
   HIP_OK(hipStreamSynchronize(st));
+  if (rule_stats) rule_stats_collect(e, n_res != 0, n_trips);
   float ms = 0, mms = 0;
   HIP_OK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
   HIP_OK(hipEventElapsedTime(&mms, e->evm0, e->evm1));
@@ -7968,7 +8000,11 @@ static void run_batch(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *bytes
     bjx_engine *e;
     ~Reset() { e->want_counters = false; }
   } reset{e};
-  if (!match_phase(e, rs, bytes, n, now_ns, flags, out)) { e->counters_fresh = false; return; }
+  if (!match_phase(e, rs, bytes, n, now_ns, flags, out)) {
+    e->counters_fresh = false;
+    rule_stats_close_empty(e, flags);
+    return;
+  }
   e->want_counters = false;
   if (e->bc.n_ev) {
     rate_limit_stage(e, e->bind, local_evsrc(e), e->bc.n_el, e->bc.el_bytes, e->bc.n_ev, e->ev_el.p, e->ev_rule.p,
@@ -8157,7 +8193,10 @@ extern "C" int bjx_finish_batch(bjx_engine *e, const uint8_t *d_outcomes, uint32
     const BatchCtx &c = e->bc;
     memset(out, 0, sizeof *out);
     e->batch_open = false;
-    if (!c.live) return BJX_OK;
+    if (!c.live) {
+      rule_stats_close_empty(e, flags);
+      return BJX_OK;
+    }
     if (c.n_ev) {
       if (!e->partitioned || e->pk_n_ev != c.n_ev || !d_outcomes) throw BjxError(BJX_ERR_ARG, "bjx_finish_batch without a packed batch");
       e->ev_out.ensure(c.n_ev);
@@ -8226,7 +8265,10 @@ extern "C" int bjx_finish_batch_trips(bjx_engine *e, const uint32_t *d_trips, ui
     const BatchCtx &c = e->bc;
     memset(out, 0, sizeof *out);
     e->batch_open = false;
-    if (!c.live) return BJX_OK;
+    if (!c.live) {
+      rule_stats_close_empty(e, flags);
+      return BJX_OK;
+    }
     if (c.n_ev) {
       if (!e->partitioned || e->pk_n_ev != c.n_ev) throw BjxError(BJX_ERR_ARG, "bjx_finish_batch_trips without a packed batch");
       if (n > c.n_ev) throw BjxError(BJX_ERR_ARG, "bjx_finish_batch_trips: more trips than packed events");
@@ -8363,6 +8405,17 @@ extern "C" int bjx_debug_set_slot_cache(bjx_engine *e, int on) {
   e->dbg_slot_cache = on < 0 ? -1 : on != 0;
   e->bound_uid = 0;  // the next batch re-binds and applies it
   return BJX_OK;
+}
+extern "C" int bjx_debug_set_rule_stats_lds(bjx_engine *e, uint32_t max_rules) {
+  if (!e) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->rs_lds_rules = max_rules;
+  return BJX_OK;
+}
+extern "C" int bjx_debug_rule_stats_path(bjx_engine *e) {
+  if (!e) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  return (int)e->rs_path;
 }
 extern "C" size_t bjx_debug_phase_ms(bjx_engine *e, double *out, size_t cap) {
   if (!e) return 0;

@@ -101,6 +101,9 @@ struct Part {
 
 }  // namespace
 
+// engine.hip, library-internal: the serial number a ruleset got at compile time
+extern "C" uint64_t bjx_internal_ruleset_serial(const bjx_ruleset *rs);
+
 struct bjx_node {
   std::vector<Part> parts;
   std::vector<ncclComm_t> comms;  // RCCL clique over the engines' GPUs (empty: peer copies)
@@ -123,6 +126,13 @@ struct bjx_node {
   // the last bjx_node_state_query's merged answer
   std::vector<bjx_state_row> q_rows;
   std::vector<uint8_t> q_bytes;
+  // per-rule counts (BJX_RULE_STATS): the engines' arrays summed, for the last
+  // batch and over every flagged batch since its ruleset came into use
+  bool rs_counted = false;
+  std::vector<bjx_rule_stat> rs_last, rs_total;
+  uint64_t rs_uid = 0;  // ruleset serial the totals are keyed to (0: none)
+  uint64_t rs_last_lines = 0, rs_batches = 0, rs_lines = 0;
+  double rs_last_ms = 0, rs_ms = 0;
 };
 
 namespace {
@@ -422,6 +432,47 @@ void merge_bans(bjx_node *n, const std::vector<uint64_t> &trip_base) {
   });
 }
 
+// The engines' per-rule counts of the batch just closed, summed: engine k
+// counted chunk k's lines.  Then the node's totals, keyed like an engine's to
+// the serial number of the batch's ruleset.
+void sum_rule_stats(bjx_node *n, const bjx_ruleset *rs) {
+  const size_t N = n->parts.size();
+  n->rs_last.clear();
+  n->rs_last_lines = 0;
+  n->rs_last_ms = 0;
+  const uint64_t uid = bjx_internal_ruleset_serial(rs);
+  for (size_t k = 0; k < N; ++k) {
+    bjx_engine *e = n->parts[k].e;
+    bjx_rule_stats s{};
+    const int rc = bjx_batch_rule_stats(e, &s);
+    if (rc != BJX_OK) fail(rc, "engine " + std::to_string(k) + ": " + bjx_engine_last_error(e));
+    if (k == 0) n->rs_last.assign(s.n_rules, bjx_rule_stat{});
+    else if (s.n_rules != n->rs_last.size()) fail(BJX_ERR_DEVICE, "internal: the engines counted different rulesets");
+    for (uint64_t r = 0; r < s.n_rules; ++r) {
+      n->rs_last[r].matches += s.rules[r].matches;
+      n->rs_last[r].skip_host += s.rules[r].skip_host;
+      n->rs_last[r].trips += s.rules[r].trips;
+    }
+    n->rs_last_lines += s.n_lines;
+    n->rs_last_ms = std::max(n->rs_last_ms, s.device_ms);
+  }
+  if (n->rs_uid != uid || n->rs_total.size() != n->rs_last.size()) {
+    n->rs_total.assign(n->rs_last.size(), bjx_rule_stat{});
+    n->rs_uid = uid;
+    n->rs_batches = n->rs_lines = 0;
+    n->rs_ms = 0;
+  }
+  for (size_t r = 0; r < n->rs_last.size(); ++r) {
+    n->rs_total[r].matches += n->rs_last[r].matches;
+    n->rs_total[r].skip_host += n->rs_last[r].skip_host;
+    n->rs_total[r].trips += n->rs_last[r].trips;
+  }
+  ++n->rs_batches;
+  n->rs_lines += n->rs_last_lines;
+  n->rs_ms += n->rs_last_ms;
+  n->rs_counted = true;
+}
+
 void run_batch(bjx_node *n, const bjx_ruleset *rs, const uint8_t *const *chunks, const size_t *lens, int64_t now_ns,
                uint32_t flags, bjx_batch_result *out) {
   const size_t N = n->parts.size();
@@ -589,6 +640,14 @@ void run_batch(bjx_node *n, const bjx_ruleset *rs, const uint8_t *const *chunks,
   *out = r;
 }
 
+// run_batch, then the engines' per-rule counts when the batch asked for them
+void run_counted(bjx_node *n, const bjx_ruleset *rs, const uint8_t *const *chunks, const size_t *lens, int64_t now_ns,
+                 uint32_t flags, bjx_batch_result *out) {
+  n->rs_counted = false;
+  run_batch(n, rs, chunks, lens, now_ns, flags, out);
+  if (flags & BJX_RULE_STATS) sum_rule_stats(n, rs);
+}
+
 }  // namespace
 
 extern "C" int bjx_node_create(const int *devices, size_t n_devices, const bjx_engine_options *opts, bjx_node **out,
@@ -713,7 +772,7 @@ extern "C" int bjx_node_process_chunks(bjx_node *n, const bjx_ruleset *rs, const
   if (!rs || !out || !chunks || !lens || !(flags & BJX_INPUT_DEVICE)) return BJX_ERR_ARG;
   return guarded(n, [&]() -> int {
     memset(out, 0, sizeof *out);
-    run_batch(n, rs, chunks, lens, now_ns, flags, out);
+    run_counted(n, rs, chunks, lens, now_ns, flags, out);
     return BJX_OK;
   });
 }
@@ -742,7 +801,46 @@ extern "C" int bjx_node_process_batch(bjx_node *n, const bjx_ruleset *rs, const 
       lens[k] = e - b;
       b = e;
     }
-    run_batch(n, rs, ptr.data(), lens.data(), now_ns, flags, out);
+    run_counted(n, rs, ptr.data(), lens.data(), now_ns, flags, out);
+    return BJX_OK;
+  });
+}
+
+extern "C" int bjx_node_batch_rule_stats(bjx_node *n, bjx_rule_stats *out) {
+  if (!out) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    memset(out, 0, sizeof *out);
+    if (!n->rs_counted) fail(BJX_ERR_ARG, "bjx_node_batch_rule_stats: the last batch ran without BJX_RULE_STATS");
+    out->n_rules = n->rs_last.size();
+    out->rules = out->n_rules ? n->rs_last.data() : nullptr;
+    out->n_batches = 1;
+    out->n_lines = n->rs_last_lines;
+    out->device_ms = n->rs_last_ms;
+    return BJX_OK;
+  });
+}
+
+extern "C" int bjx_node_rule_stats_total(bjx_node *n, bjx_rule_stats *out) {
+  if (!out) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    memset(out, 0, sizeof *out);
+    if (!n->rs_uid) return BJX_OK;  // no flagged batch yet
+    out->n_rules = n->rs_total.size();
+    out->rules = out->n_rules ? n->rs_total.data() : nullptr;
+    out->n_batches = n->rs_batches;
+    out->n_lines = n->rs_lines;
+    out->device_ms = n->rs_ms;
+    return BJX_OK;
+  });
+}
+
+// the node's own totals; each engine's are its own (bjx_rule_stats_reset on bjx_node_engine)
+extern "C" int bjx_node_rule_stats_reset(bjx_node *n) {
+  return guarded(n, [&]() -> int {
+    n->rs_total.clear();
+    n->rs_uid = 0;
+    n->rs_batches = n->rs_lines = 0;
+    n->rs_ms = 0;
     return BJX_OK;
   });
 }

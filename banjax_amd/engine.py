@@ -171,14 +171,15 @@ class Engine:
 
     def process(self, rs: Ruleset, data, now_ns: int, copy_results: bool = False, device_ptr: Optional[int] = None,
                 nbytes: Optional[int] = None, emit_bans: bool = False, ban_log: bool = True,
-                compact_trips: bool = False) -> BatchOutput:
+                compact_trips: bool = False, rule_stats: bool = False) -> BatchOutput:
         """consumeLine over every complete line of `data` (bytes) or of a device
         buffer (device_ptr, nbytes) already resident in HBM.  emit_bans with
         ban_log=False: the per-IP decision records only (BJX_BAN_RECORDS_ONLY).
-        compact_trips: trips as 8-byte words (BatchOutput.trips_compact)."""
+        compact_trips: trips as 8-byte words (BatchOutput.trips_compact).
+        rule_stats: also count the batch's RuleResults per rule (rule_stats())."""
         res = _lib.BatchResult()
         flags = (_lib.COPY_RESULTS if copy_results else 0) | (_lib.EMIT_BANS if emit_bans else 0) | \
-            (_lib.TRIPS_COMPACT if compact_trips else 0)
+            (_lib.TRIPS_COMPACT if compact_trips else 0) | (_lib.RULE_STATS if rule_stats else 0)
         if emit_bans and not ban_log:
             flags |= _lib.BAN_RECORDS_ONLY
         if device_ptr is not None:
@@ -235,16 +236,18 @@ class Engine:
                     "apply_events_trips")
         return [cnt[k] for k in range(n)]
 
-    def finish_trips(self, trips_ptr: int, n: int, emit_bans: bool = False) -> BatchOutput:
+    def finish_trips(self, trips_ptr: int, n: int, emit_bans: bool = False, rule_stats: bool = False) -> BatchOutput:
         res = _lib.BatchResult()
-        flags = _lib.EMIT_BANS if emit_bans else 0
+        flags = (_lib.EMIT_BANS if emit_bans else 0) | (_lib.RULE_STATS if rule_stats else 0)
         self._check(_lib.lib().bjx_finish_batch_trips(self._h, C.c_void_p(trips_ptr), n, flags, C.byref(res)),
                     "finish_batch_trips")
         return BatchOutput(res, False)
 
-    def finish(self, outcomes_ptr: int, copy_results: bool = False, emit_bans: bool = False) -> BatchOutput:
+    def finish(self, outcomes_ptr: int, copy_results: bool = False, emit_bans: bool = False,
+               rule_stats: bool = False) -> BatchOutput:
         res = _lib.BatchResult()
-        flags = (_lib.COPY_RESULTS if copy_results else 0) | (_lib.EMIT_BANS if emit_bans else 0)
+        flags = (_lib.COPY_RESULTS if copy_results else 0) | (_lib.EMIT_BANS if emit_bans else 0) | \
+            (_lib.RULE_STATS if rule_stats else 0)
         self._check(_lib.lib().bjx_finish_batch(self._h, C.c_void_p(outcomes_ptr), flags, C.byref(res)),
                     "finish_batch")
         return BatchOutput(res, copy_results)
@@ -389,6 +392,40 @@ class Engine:
             rows.append((blob[r.ip_off:r.ip_off + r.ip_len], blob[r.name_off:r.name_off + r.name_len], r.hits, r.start_ns))
         return {"n_matched": out.n_matched, "n_ips_matched": out.n_ips_matched, "rows": rows, "device_ms": out.device_ms}
 
+    _rule_stats = "bjx_"
+
+    def rule_stats(self, total: bool = False) -> dict:
+        """Per-rule counts of the last batch (run with rule_stats=True), or with
+        total=True of every such batch since its ruleset came into use
+        (bjx_batch_rule_stats / bjx_rule_stats_total; banjax_amd/rule_stats.py
+        is the model).  Returns {"n_batches", "n_lines", "device_ms", "rules"}:
+        rules is a numpy structured array (matches, skip_host, trips) indexed
+        by ruleset rule index, copied out of the library's memory once."""
+        import numpy as np
+        out = _lib.RuleStats()
+        name = self._rule_stats + ("rule_stats_total" if total else "batch_rule_stats")
+        self._check(getattr(_lib.lib(), name)(self._h, C.byref(out)), name)
+        if out.n_rules:
+            view = (_lib.RuleStat * out.n_rules).from_address(C.addressof(out.rules.contents))
+            rules = np.ctypeslib.as_array(view).copy()
+        else:
+            rules = np.zeros(0, dtype=np.dtype(_lib.RuleStat))
+        return {"n_batches": out.n_batches, "n_lines": out.n_lines, "device_ms": out.device_ms, "rules": rules}
+
+    def rule_stats_reset(self):
+        """Forget the totals (rule_stats(total=True) is empty until the next flagged batch)."""
+        name = self._rule_stats + "rule_stats_reset"
+        self._check(getattr(_lib.lib(), name)(self._h), name)
+
+    def debug_set_rule_stats_lds(self, max_rules: int):
+        """Test hook: LDS bins only for rulesets of at most max_rules rules (0 = default)."""
+        self._check(_lib.lib().bjx_debug_set_rule_stats_lds(self._h, max_rules), "debug_set_rule_stats_lds")
+
+    def debug_rule_stats_path(self) -> str:
+        """Where the last rule_stats=True batch binned: "lds", "global", or "none" (no results, nothing launched)."""
+        return {0: "none", 1: "lds", 2: "global"}[self._check(_lib.lib().bjx_debug_rule_stats_path(self._h),
+                                                              "debug_rule_stats_path")]
+
     def close(self):
         h = getattr(self, "_h", None)
         if h and _lib._lib is not None:
@@ -456,21 +493,23 @@ class Node:
         o, keep = _ban_options(expiring_ttl_s, disable_logging, tz_offset_s, zone)
         self._check(_lib.lib().bjx_node_set_ban_options(self._h, C.byref(o)), "node_set_ban_options")
 
-    def process(self, rs: Ruleset, data, now_ns: int, copy_results: bool = False, emit_bans: bool = False) -> BatchOutput:
+    def process(self, rs: Ruleset, data, now_ns: int, copy_results: bool = False, emit_bans: bool = False,
+                rule_stats: bool = False) -> BatchOutput:
         """consumeLine over the complete lines of a host buffer, split over the engines."""
         res = _lib.BatchResult()
-        flags = (_lib.COPY_RESULTS if copy_results else 0) | (_lib.EMIT_BANS if emit_bans else 0)
+        flags = (_lib.COPY_RESULTS if copy_results else 0) | (_lib.EMIT_BANS if emit_bans else 0) | \
+            (_lib.RULE_STATS if rule_stats else 0)
         buf = _lib.b(data)
         self._check(_lib.lib().bjx_node_process_batch(self._h, rs.handle, C.c_char_p(buf), len(buf), now_ns, flags,
                                                       C.byref(res)), "node_process_batch")
         return BatchOutput(res, copy_results)
 
     def process_chunks(self, rs: Ruleset, chunks: Sequence[Tuple[int, int]], now_ns: int, copy_results: bool = False,
-                       emit_bans: bool = False, compact_trips: bool = False) -> BatchOutput:
+                       emit_bans: bool = False, compact_trips: bool = False, rule_stats: bool = False) -> BatchOutput:
         """chunks[k] = (device pointer on engine k's GPU, bytes); all but the last end in '\\n'."""
         res = _lib.BatchResult()
         flags = (_lib.COPY_RESULTS if copy_results else 0) | (_lib.EMIT_BANS if emit_bans else 0) | _lib.INPUT_DEVICE | \
-            (_lib.TRIPS_COMPACT if compact_trips else 0)
+            (_lib.TRIPS_COMPACT if compact_trips else 0) | (_lib.RULE_STATS if rule_stats else 0)
         ptrs = (C.c_void_p * len(chunks))(*[p for p, _ in chunks])
         lens = (C.c_size_t * len(chunks))(*[n for _, n in chunks])
         self._check(_lib.lib().bjx_node_process_chunks(self._h, rs.handle, ptrs, lens, now_ns, flags, C.byref(res)),
@@ -518,6 +557,10 @@ class Node:
 
     _query = "bjx_node_state_query"
     state_query = Engine.state_query  # every shard's answer merged, IPs engine-major; an ip filter asks its owner only
+
+    _rule_stats = "bjx_node_"
+    rule_stats = Engine.rule_stats  # the engines' arrays summed; engine(k).rule_stats() has engine k's own
+    rule_stats_reset = Engine.rule_stats_reset  # the node's totals; each engine keeps its own
 
     def state_import(self, blob: bytes) -> dict:
         """Restore a snapshot taken on any number of engines: engine k takes the IPs it owns."""

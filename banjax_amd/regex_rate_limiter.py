@@ -489,6 +489,7 @@ class RegexRateLimiter:
         self.zone = zone if zone is not None else Zone.fixed(tz_offset_s)
         self.banner.zone = self.zone
         self._seen_names: Dict[str, None] = {}
+        self._stats_cfg: Optional[Config] = None  # config of the last batch consumed with rule_stats=True
         self.states = RegexRateLimitStates(self.engine, lambda: list(self._seen_names))
         self.reload(cfg)
 
@@ -527,12 +528,29 @@ class RegexRateLimiter:
     def ruleset(self) -> Ruleset:
         return self._snap.ruleset
 
-    def consume_lines(self, data: bytes, now_ns: int, want_results: bool = True):
-        """consumeLine for every complete line; returns (results, batch output)."""
+    def consume_lines(self, data: bytes, now_ns: int, want_results: bool = True, rule_stats: bool = False):
+        """consumeLine for every complete line; returns (results, batch output).
+        rule_stats: also count the batch's RuleResults per rule (rule_stats())."""
         with self._mu:
             snap = self._snap
-            out = self.engine.process(snap.ruleset, data, now_ns, copy_results=want_results, **self._ban_kw())
+            kw = dict(self._ban_kw(), rule_stats=True) if rule_stats else self._ban_kw()
+            out = self.engine.process(snap.ruleset, data, now_ns, copy_results=want_results, **kw)
+            if rule_stats:
+                self._stats_cfg = snap.config
             return self._finish(snap, data, out, now_ns, want_results)
+
+    def rule_stats(self, total: bool = True) -> dict:
+        """Matches, SkipHost matches, events and trips per rule *name* (what the
+        state is keyed by; rule_stats.by_name) of the batches consumed with
+        rule_stats=True: since the config they ran under came into use, or with
+        total=False of the last one.  {} before any such batch."""
+        from . import rule_stats as model
+        with self._mu:
+            cfg = self._stats_cfg
+            if cfg is None:
+                return {}
+            st = self.engine.rule_stats(total=total)
+            return model.by_name(cfg, st) if len(st["rules"]) else {}
 
     def expire_states(self, now_ns: int) -> dict:
         """Drop the rate-limit state no later line can hit inside its window

@@ -158,8 +158,9 @@ enum bjx_batch_flags {
   BJX_EMIT_BANS = 4,      /* also build the batch's decision updates and ban-log lines (bjx_batch_bans) */
   BJX_BAN_RECORDS_ONLY = 8, /* with BJX_EMIT_BANS: the per-IP decision records only; no LogRegexBan lines
                               are built or copied (log_bytes 0, every log_kind 0) */
-  BJX_TRIPS_COMPACT = 16    /* trips as 8-byte words in trips_compact (trips NULL): what the host cannot
+  BJX_TRIPS_COMPACT = 16,   /* trips as 8-byte words in trips_compact (trips NULL): what the host cannot
                               re-derive from its own copy of the bytes -- which line, which rule */
+  BJX_RULE_STATS = 32       /* also count the batch's RuleResults per rule (bjx_batch_rule_stats) */
 };
 
 /* BJX_TRIPS_COMPACT trip word: the line's byte offset in the batch (40 bits)
@@ -530,6 +531,47 @@ typedef struct bjx_ban_batch {
 /* The last batch's emission (valid until the next batch; needs BJX_EMIT_BANS). */
 int bjx_batch_bans(bjx_engine *e, bjx_ban_batch *out);
 
+/* ---- Per-rule statistics of a batch (no counterpart in the reference, whose
+   host could count inside its per-line loop; here the RuleResults exist only
+   as per-line masks in HBM, so they are counted there and a few counters per
+   rule come back).  A batch closed with BJX_RULE_STATS -- bjx_process_batch,
+   bjx_finish_batch, bjx_finish_batch_trips and the node batch calls read the
+   flag; bjx_match_batch ignores it -- also counts, per ruleset rule index,
+   the RuleResults of the closing engine's own lines: every one (matches),
+   those that were SkipHost and never reached Apply (skip_host; the rule's
+   events are matches - skip_host) and those whose RateLimitResult came out
+   Exceeded (trips; an event applied on another owner counts at the engine
+   that matched the line, as its trip does).  The counts do not depend on
+   BJX_COPY_RESULTS, BJX_EMIT_BANS or BJX_TRIPS_COMPACT.  A batch without any
+   RuleResult, or of zero bytes, gives n_rules rows of zeros.
+
+   bjx_batch_rule_stats: the last batch (n_batches 1); BJX_ERR_ARG when it ran
+   without the flag.  bjx_rule_stats_total: the sum over every flagged batch
+   since the ruleset came into use: the totals start over when a flagged batch
+   runs with another ruleset than the flagged batch before it (rule indices
+   mean nothing across rulesets); before any flagged batch, and after
+   bjx_rule_stats_reset, n_rules 0 and rules NULL.  An unflagged batch changes
+   neither the totals nor what they are keyed to.  The library checks on the
+   host that the rows add up to the batch's n_results, n_events and n_trips
+   (BJX_ERR_DEVICE "internal: ..." otherwise).  The calls take the engine lock;
+   the node calls wait for the node batch and return the sum of the engines'
+   arrays, device_ms the slowest engine's.  Without the flag a batch launches,
+   allocates and copies nothing for this. */
+typedef struct bjx_rule_stat {   /* 24 B, one per rule of the batch's ruleset, by ruleset rule index */
+  uint64_t matches;    /* RuleResults of the rule (RegexMatch), SkipHost ones included */
+  uint64_t skip_host;  /* of those, SkipHost: they never reached Apply; events = matches - skip_host */
+  uint64_t trips;      /* of those, RateLimitResult.Exceeded */
+} bjx_rule_stat;
+typedef struct bjx_rule_stats {
+  uint64_t n_rules;             /* bjx_ruleset_num_rules of the ruleset counted */
+  const bjx_rule_stat *rules;   /* engine-owned (node-owned), valid until the next batch / next call of the same kind */
+  uint64_t n_batches, n_lines;  /* batches and complete lines summed in (1 and the batch's n_lines for the last batch) */
+  double device_ms;             /* HIP events around the counting alone; totals: summed */
+} bjx_rule_stats;
+int bjx_batch_rule_stats(bjx_engine *e, bjx_rule_stats *out);
+int bjx_rule_stats_total(bjx_engine *e, bjx_rule_stats *out);
+int bjx_rule_stats_reset(bjx_engine *e);
+
 /* ---- Node: the GPUs of one host behind one handle.  The Go
    host keeps ONE RegexRateLimitStates (rate_limit.go:19-28, created once in
    banjax.go:80) fed by ONE consumer goroutine (regex_rate_limiter.go:54-77);
@@ -601,6 +643,12 @@ int bjx_node_state_import(bjx_node *n, const uint8_t *snap, uint64_t len, bjx_sn
    bjx_node_state_expire does; rows and bytes are node-owned until the next
    query on the node. */
 int bjx_node_state_query(bjx_node *n, const bjx_state_filter *f, bjx_state_rows *out);
+/* bjx_batch_rule_stats / bjx_rule_stats_total / bjx_rule_stats_reset over the
+   node: the engines' arrays summed (engine k counted chunk k's lines),
+   n_lines summed, device_ms the slowest engine's (totals: those summed). */
+int bjx_node_batch_rule_stats(bjx_node *n, bjx_rule_stats *out);
+int bjx_node_rule_stats_total(bjx_node *n, bjx_rule_stats *out);
+int bjx_node_rule_stats_reset(bjx_node *n);
 
 int bjx_abi_version(void);
 

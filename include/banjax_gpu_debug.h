@@ -69,6 +69,13 @@ int bjx_debug_set_dfa_state_cap(uint32_t cap);
    block-cooperative NFA (kRuleNfaWide), process-wide; clears the
    compiled-pattern cache. */
 int bjx_debug_force_wide_nfa(int on);
+/* Test hook: BJX_RULE_STATS bins in LDS only for rulesets of at most max_rules
+   rules (0 = default, the LDS a block may have); past it the counting kernels
+   add straight to the global counters. */
+int bjx_debug_set_rule_stats_lds(bjx_engine *e, uint32_t max_rules);
+/* where the engine's last BJX_RULE_STATS batch binned: 1 LDS, 2 the global
+   counters, 0 nothing was launched (no results) */
+int bjx_debug_rule_stats_path(bjx_engine *e);
 #ifdef __cplusplus
 }
 #endif
