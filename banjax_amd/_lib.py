@@ -111,6 +111,7 @@ EXPORTS = [
     "bjx_state_export_bound", "bjx_state_export", "bjx_state_import",
     "bjx_node_state_export_bound", "bjx_node_state_export", "bjx_node_state_import",
     "bjx_state_query", "bjx_node_state_query",
+    "bjx_state_remove", "bjx_node_state_remove",
     "bjx_batch_rule_stats", "bjx_rule_stats_total", "bjx_rule_stats_reset",
     "bjx_node_batch_rule_stats", "bjx_node_rule_stats_total", "bjx_node_rule_stats_reset",
 ]
@@ -154,6 +155,13 @@ class StateRows(C.Structure):
     _fields_ = [("n_matched", C.c_uint64), ("n_ips_matched", C.c_uint64), ("n_rows", C.c_uint64),
                 ("rows", C.POINTER(StateRow)), ("bytes", C.c_void_p), ("n_bytes", C.c_uint64),
                 ("device_ms", C.c_double)]
+
+
+class RemoveStats(C.Structure):
+    """bjx_remove_stats: what one bjx_state_remove found, dropped and freed (80 B)."""
+    _fields_ = [(k, C.c_uint64) for k in ("states_before", "states_dropped", "ips_before", "ips_dropped", "ips_found",
+                                            "arena_bytes_before", "arena_bytes_after", "device_bytes_before",
+                                            "device_bytes_after")] + [("device_ms", C.c_double)]
 
 
 class RuleStat(C.Structure):
@@ -322,6 +330,9 @@ def lib():
     for name in ("bjx_state_query", "bjx_node_state_query"):
         f = getattr(L, name)
         f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(StateRows)]
+    for name in ("bjx_state_remove", "bjx_node_state_remove"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(Str), sz, C.POINTER(RemoveStats)]
     for pre in ("bjx_", "bjx_node_"):
         for name in ("batch_rule_stats", "rule_stats_total"):
             f = getattr(L, pre + name)

@@ -46,6 +46,7 @@
 #include "bans.h"
 #include "snapshot.h"
 #include "state_query.h"
+#include "state_remove.h"
 
 using namespace bjx;
 

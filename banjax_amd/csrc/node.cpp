@@ -45,6 +45,7 @@
 #include "bjx_common.h"
 #include "snapshot.h"
 #include "state_query.h"
+#include "state_remove.h"
 
 namespace {
 
@@ -1049,6 +1050,37 @@ extern "C" int bjx_node_state_query(bjx_node *n, const bjx_state_filter *f, bjx_
       ans.push_back(a);
     }
     bjx_query::merge(ans, f->order, f->limit, out, &n->q_rows, &n->q_bytes);
+    return BJX_OK;
+  });
+}
+
+// every shard with the same filter and the whole list (an IP lives on one
+// shard, the others do not find it).  Every shard is asked even when one
+// fails: the first failure is returned, the shards done stay done, and the
+// caller repeats the call (removal is idempotent)
+extern "C" int bjx_node_state_remove(bjx_node *n, const bjx_state_filter *f, const bjx_str *ips, size_t n_ips,
+                                     bjx_remove_stats *out) {
+  if (!n) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    if (const char *why = bjx_remove::check_args(f, ips, n_ips)) fail(BJX_ERR_ARG, std::string("bjx_node_state_remove: ") + why);
+    bjx_remove_stats t{};
+    int first_rc = BJX_OK;
+    std::string first_msg;
+    for (size_t k = 0; k < n->parts.size(); ++k) {
+      bjx_engine *e = n->parts[k].e;
+      bjx_remove_stats s{};
+      const int rc = bjx_state_remove(e, f, ips, n_ips, &s);
+      if (rc != BJX_OK) {
+        if (first_rc == BJX_OK) {
+          first_rc = rc;
+          first_msg = "engine " + std::to_string(k) + ": " + bjx_engine_last_error(e);
+        }
+        continue;
+      }
+      bjx_remove::add(&t, s);
+    }
+    if (first_rc != BJX_OK) fail(first_rc, first_msg);
+    if (out) *out = t;
     return BJX_OK;
   });
 }

@@ -16,6 +16,7 @@
 //   mark_and_scan / scan_kept     keep[], dense new ids, arena offsets, totals
 //   NewTables                     the new arrays, owned until installed
 //   install                       the swap and everything it resets
+//   rebuild_kept                  expiry's and removal's second half: new tables, kept IPs and states, the swap
 #pragma once
 
 namespace {
@@ -443,6 +444,86 @@ __global__ void k_qry_bytes(uint64_t n_rows, uint64_t n_cand, const ulonglong2 *
   for (uint32_t k = 0; k < nl; ++k) out[d + il + k] = name_bytes[no + k];
 }
 
+// removal (bjx_state_remove; argument checks, the packed list, the node's sum:
+// state_remove.h): the expiry's rebuild with another predicate.  A state goes
+// when the query's filter passes it and, with a list, sel[its IP id] is set;
+// k_rm_ips sets sel[] from the listed bytes, k_rm_mark is k_exp_mark and
+// k_rm_st is k_exp_st with that predicate.  Everything between them is the
+// expiry's own (k_exp_len, scan_kept, k_exp_arena, k_exp_ip, install).
+//
+// One lane per listed IP, entries [first, first + n_list) of the packed list
+// (entry k: bytes[off[k], off[k + 1]); 4 readable bytes past the last one for
+// hash_bytes' word loads).  The IP is looked up as ip_claim_line looks up an IP
+// of an earlier batch and k_imp_verify checks one: hash (under the debug mask
+// as k_imp_place applies it), key16, arena bytes past 15 bytes, id < n_ips.
+// sel[id] = 1: every writer stores the same value.
+__global__ void k_rm_ips(uint32_t first, uint32_t n_list, const uint32_t *__restrict__ off, const uint8_t *__restrict__ bytes,
+                         uint64_t hmask, const IpSlot *__restrict__ ipt, uint64_t ip_mask, uint64_t n_ips,
+                         const uint64_t *__restrict__ ip_off, const uint32_t *__restrict__ ip_len,
+                         const uint8_t *__restrict__ arena, uint64_t arena_used, uint32_t *__restrict__ sel) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_list) return;
+  const uint32_t a = off[first + i], len = off[first + i + 1] - a;
+  const uint8_t *src = bytes + a;
+  const uint4 k16 = ip_key16_bytes(src, len);
+  uint64_t h = hash_bytes(src, len);
+  if (hmask) h = (h & hmask) | 1ull;
+  uint64_t j = h & ip_mask;
+  for (uint64_t step = 0; step <= ip_mask; ++step) {
+    const IpSlot v = ipt[j];
+    if (v.hash == 0) return;
+    if (v.hash == h && v.id < n_ips && key16_eq(v.key16, k16)) {
+      bool same = len <= 15;
+      if (!same && ip_len[v.id] == len) {
+        const uint64_t so = ip_off[v.id];
+        same = so + len <= arena_used && bytes_eq(arena + so, src, len);
+      }
+      if (same) {
+        sel[v.id] = 1u;
+        return;  // (an IP has one slot)
+      }
+    }
+    j = (j + 1) & ip_mask;
+  }
+}
+// the one predicate of the mark and the re-insert: v (live) is to be dropped
+__device__ __forceinline__ bool rm_selected(const StSlot &v, const QFilter &F, uint64_t n_ips, uint32_t n_names,
+                                            const uint32_t *__restrict__ sel) {
+  return q_pass(v, F, n_ips, n_names) && (!sel || sel[(v.key >> 24) - 1]);
+}
+// grid-stride; a live slot that is not selected keeps its IP (keep[id] = 1);
+// cnt[0] += states kept, cnt[1] += states selected (one atomic each per block)
+__global__ __launch_bounds__(kBlock) void k_rm_mark(uint64_t st_cap, const StSlot *__restrict__ st, QFilter F, uint64_t n_ips,
+                                                    uint32_t n_names, const uint32_t *__restrict__ sel,
+                                                    uint32_t *__restrict__ keep, unsigned long long *__restrict__ cnt) {
+  uint64_t kept = 0, gone = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < st_cap; i += (uint64_t)gridDim.x * blockDim.x) {
+    const StSlot v = st[i];
+    if (!st_survives(v, INT64_MIN, n_ips)) continue;
+    if (rm_selected(v, F, n_ips, n_names, sel)) {
+      ++gone;
+    } else {
+      keep[(v.key >> 24) - 1] = 1u;  // every writer stores the same value
+      ++kept;
+    }
+  }
+  block_sum2(kept, gone);
+  if (threadIdx.x == 0 && kept) atomicAdd(&cnt[0], (unsigned long long)kept);
+  if (threadIdx.x == 0 && gone) atomicAdd(&cnt[1], (unsigned long long)gone);
+}
+// the live, unselected slots under their IPs' new ids (k_exp_st's shape: the
+// payload stores stay outside fresh_put_st's probe loop)
+__global__ void k_rm_st(uint64_t old_cap, const StSlot *__restrict__ o, QFilter F, uint64_t n_ips, uint32_t n_names,
+                        const uint32_t *__restrict__ sel, const uint32_t *__restrict__ nid, StSlot *__restrict__ nt,
+                        uint64_t nmask) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= old_cap) return;
+  const StSlot v = o[i];
+  if (!st_survives(v, INT64_MIN, n_ips) || rm_selected(v, F, n_ips, n_names, sel)) return;
+  const uint64_t key = ((uint64_t)(nid[(v.key >> 24) - 1] + 1) << 24) | (v.key & 0xFFFFFFull);
+  fresh_put_st(nt, nmask, key, v.hits, v.start, v.valid);
+}
+
 // snapshot import (bjx_state_import).  err[c] = 1 (plain stores of one value)
 // when check c fails: 1 ip_off not monotone from 0, 2 ip_off[n_ips] !=
 // ip_bytes, 3 record ip >= n_ips, 4 record name >= n_names, 5 records not
@@ -829,6 +910,37 @@ void mark_and_scan(bjx_engine *e, Kept &K, int64_t cutoff, hipEvent_t ev_begin, 
   scan_kept(e, K, n_ips, used, e->st_cap, ev_end, what);
 }
 
+// Expiry's and removal's second half, between ev_begin and ev_end: the new
+// tables by growth's sizing rule on what K keeps (never below the capacity the
+// engine was created with, never above the present one; allocated before the
+// old ones go, so BJX_ERR_NOMEM leaves the state untouched), the kept IPs'
+// bytes and slots under their new ids, the kept states through put_states(nw)
+// -- the caller's kernel, which knows what survives -- and the swap.
+// (n_ips, used: the counters K was taken from)
+template <typename PutStates>
+void rebuild_kept(bjx_engine *e, const Kept &K, uint64_t n_ips, uint64_t used, hipEvent_t ev_begin, hipEvent_t ev_end,
+                  const char *nomem_msg, PutStates put_states) {
+  State &S = e->S;
+  hipStream_t st = e->stream;
+  NewTables nw(clamp_cap(table_cap_for(K.ips), e->ip_cap0, e->ip_cap), clamp_cap(table_cap_for(K.states), e->st_cap0, e->st_cap),
+               clamp_cap(arena_cap_for(K.bytes), e->arena_cap0, S.arena_cap), nomem_msg);
+  HIP_OK(hipEventRecord(ev_begin, st));
+  nw.clear(st);
+  if (n_ips) {
+    hipLaunchKernelGGL(k_exp_arena, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, K.keep, K.nid, K.noff, S.ip_off, S.ip_len,
+                       S.arena, used, nw.arena, nw.arena_cap, nw.ip_off, nw.ip_len);
+    HIP_OK(hipGetLastError());
+  }
+  put_states(nw);
+  HIP_OK(hipGetLastError());
+  hipLaunchKernelGGL(k_exp_ip, dim3(grid_for(e->ip_cap)), dim3(kBlock), 0, st, e->ip_cap, S.ip, n_ips, K.keep, K.nid, nw.ip,
+                     nw.ip_cap - 1);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord(ev_end, st));
+  const uint64_t totals[3] = {K.ips, K.bytes, K.states};
+  install(e, nw, totals);
+}
+
 // ---- snapshot: bjx_state_export / bjx_state_import (format and host checks: snapshot.h)
 struct SnapEvents {
   hipEvent_t ev[8] = {};
@@ -993,27 +1105,11 @@ extern "C" int bjx_state_expire(bjx_engine *e, int64_t cutoff_ns, bjx_expire_sta
     if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_expire: no device memory for the scan buffers");
     mark_and_scan(e, K, cutoff_ns, E.ev[0], E.ev[1], "internal: expiry counts exceed the tables");
 
-    // the new tables: growth's sizing rule on the survivors, never below the
-    // capacity the engine was created with and never above the present one
-    NewTables nw(clamp_cap(table_cap_for(K.ips), e->ip_cap0, e->ip_cap), clamp_cap(table_cap_for(K.states), e->st_cap0, e->st_cap),
-                 clamp_cap(arena_cap_for(K.bytes), e->arena_cap0, S.arena_cap),
-                 "bjx_state_expire: no device memory for the new tables (state unchanged)");
-    HIP_OK(hipEventRecord(E.ev[2], st));
-    nw.clear(st);
-    if (n_ips) {
-      hipLaunchKernelGGL(k_exp_arena, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, K.keep, K.nid, K.noff, S.ip_off, S.ip_len,
-                         S.arena, used, nw.arena, nw.arena_cap, nw.ip_off, nw.ip_len);
-      HIP_OK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_exp_st, dim3(grid_for(e->st_cap)), dim3(kBlock), 0, st, e->st_cap, S.st, cutoff_ns, n_ips, K.nid, nw.st,
-                       nw.st_cap - 1);
-    HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(k_exp_ip, dim3(grid_for(e->ip_cap)), dim3(kBlock), 0, st, e->ip_cap, S.ip, n_ips, K.keep, K.nid, nw.ip,
-                       nw.ip_cap - 1);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(E.ev[3], st));
-    const uint64_t totals[3] = {K.ips, K.bytes, K.states};
-    install(e, nw, totals);
+    rebuild_kept(e, K, n_ips, used, E.ev[2], E.ev[3], "bjx_state_expire: no device memory for the new tables (state unchanged)",
+                 [&](NewTables &nw) {
+                   hipLaunchKernelGGL(k_exp_st, dim3(grid_for(e->st_cap)), dim3(kBlock), 0, st, e->st_cap, S.st, cutoff_ns, n_ips,
+                                      K.nid, nw.st, nw.st_cap - 1);
+                 });
     if (out) {
       out->states_before = n_st; out->states_dropped = n_st - std::min<uint64_t>(n_st, K.states);
       out->ips_before = n_ips; out->ips_dropped = n_ips - K.ips;
@@ -1022,6 +1118,128 @@ extern "C" int bjx_state_expire(bjx_engine *e, int64_t cutoff_ns, bjx_expire_sta
       out->device_bytes_after = state_device_bytes(e->ip_cap, e->st_cap, S.arena_cap);
       out->device_ms = E.ms(0, 1) + E.ms(2, 3);
     }
+    return BJX_OK;
+  });
+}
+
+// Removal: the listed IPs are found on the device (sel[]), one pass over the
+// state table marks the IPs that keep a state and counts the states kept and
+// selected, and when any state is selected the expiry's rebuild follows with
+// k_rm_st in k_exp_st's place.  Nothing selected: the tables were only read and
+// stay as they are.
+extern "C" int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const bjx_str *ips, size_t n_ips,
+                                bjx_remove_stats *out) {
+  return guarded(e, [&]() -> int {
+    if (const char *why = bjx_remove::check_args(f, ips, n_ips)) throw BjxError(BJX_ERR_ARG, std::string("bjx_state_remove: ") + why);
+    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_remove between bjx_match_batch and its bjx_finish_batch");
+    bjx_remove::List L;
+    bjx_remove::pack(*f, ips, n_ips, &L);
+    HIP_OK(hipDeviceSynchronize());  // nothing of an earlier batch may land after the rebuild
+    State &S = e->S;
+    hipStream_t st = e->stream;
+    SnapEvents E;
+    E.create();
+    read_counters(e);
+    const uint64_t n_ips_held = e->host_counters[0], used = e->host_counters[1], n_st = e->host_counters[2];
+    if (n_ips_held >= 0x7FFFFFFFull) throw BjxError(BJX_ERR_CAPACITY, "more than 2^31 distinct IPs");
+    const uint32_t n_names = (uint32_t)e->names.size();
+    bjx_remove_stats R{};
+    R.states_before = n_st; R.ips_before = n_ips_held;
+    R.arena_bytes_before = R.arena_bytes_after = used;
+    R.device_bytes_before = R.device_bytes_after = state_device_bytes(e->ip_cap, e->st_cap, S.arena_cap);
+
+    // what no state can pass (not errors): an empty window, a name never
+    // interned, a filter ip the list does not hold, an engine without state
+    QFilter F{f->min_hits, f->min_start_ns, f->max_start_ns, kNone, 0u};
+    bool nothing = L.nothing || bjx_query::empty_window(*f) || !n_ips_held || !n_st;
+    if (f->name.ptr) {
+      auto it = e->name_ids.find(std::string(f->name.ptr, f->name.len));
+      if (it == e->name_ids.end()) nothing = true;
+      else F.name = it->second;
+    }
+    const bool count_found = L.n_list != 0 && n_ips_held != 0;  // ips_found is asked for
+    if (nothing && !count_found) {
+      if (out) *out = R;
+      return BJX_OK;
+    }
+
+    ExpAlloc tmp;
+    Kept K(tmp, n_ips_held);
+    uint32_t *sel = L.restrict ? tmp.get<uint32_t>(n_ips_held + 1) : nullptr;
+    uint32_t *d_sum = tmp.get<uint32_t>(4);
+    // the list on the device: u32 off[entries + 1], then the bytes (word aligned, 4 readable bytes past them)
+    const uint64_t off_bytes = ((uint64_t)L.n_entries() + 1) * 4;
+    const uint64_t list_bytes = L.restrict ? off_bytes + L.bytes.size() : 0;
+    uint8_t *d_list = L.restrict ? tmp.get<uint8_t>(((list_bytes + 3) & ~3ull) + 16) : nullptr;
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_remove: no device memory for the scan buffers");
+    if (L.restrict) {
+      std::vector<uint8_t> img(list_bytes);
+      memcpy(img.data(), L.off.data(), off_bytes);
+      if (!L.bytes.empty()) memcpy(img.data() + off_bytes, L.bytes.data(), L.bytes.size());
+      snap_copy_in(e, d_list, img.data(), list_bytes);  // one upload; waits for the stream
+    }
+    const uint32_t *d_off = reinterpret_cast<const uint32_t *>(d_list);
+    const uint8_t *d_bytes = d_list ? d_list + off_bytes : nullptr;
+    auto find_ips = [&](uint32_t first, uint32_t count) {
+      HIP_OK(hipMemsetAsync(sel, 0, (n_ips_held + 1) * 4, st));
+      if (!count) return;
+      hipLaunchKernelGGL(k_rm_ips, dim3(grid_for(count)), dim3(kBlock), 0, st, first, count, d_off, d_bytes, e->dbg_hash_mask, S.ip,
+                         S.ip_mask, n_ips_held, S.ip_off, S.ip_len, S.arena, used, sel);
+      HIP_OK(hipGetLastError());
+    };
+
+    // 1. sel[]: the caller's list first (ips_found), then, when the filter
+    // names an IP, that IP alone
+    e->chk.ensure(8);
+    uint32_t found = 0;
+    HIP_OK(hipEventRecord(E.ev[0], st));
+    HIP_OK(hipMemsetAsync(e->chk.p, 0, 16, st));
+    if (count_found) {
+      HIP_OK(hipMemsetAsync(d_sum, 0, 16, st));
+      find_ips(0, L.n_list);
+      cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceReduce::Sum(t, b, sel, d_sum, (int)n_ips_held, st); });
+      pin_get(e, &found, d_sum, 4);
+    }
+    if (nothing) {
+      HIP_OK(hipEventRecord(E.ev[1], st));
+      pin_sync(e);
+      R.ips_found = found;
+      R.device_ms = E.ms(0, 1);
+      if (out) *out = R;
+      return BJX_OK;
+    }
+    if (L.restrict && (L.has_ip || !count_found)) find_ips(L.sel_first, L.sel_count);
+
+    // 2. the IPs that keep a state, the states kept and selected, the scans
+    unsigned long long selected = 0;
+    HIP_OK(hipMemsetAsync(K.keep, 0, (n_ips_held + 1) * 4, st));
+    hipLaunchKernelGGL(k_rm_mark, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st, e->st_cap,
+                       S.st, F, n_ips_held, n_names, sel, K.keep, e->chk.p);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_exp_len, dim3(grid_for(n_ips_held + 1)), dim3(kBlock), 0, st, n_ips_held, K.keep, S.ip_len, K.klen);
+    HIP_OK(hipGetLastError());
+    pin_get(e, &selected, e->chk.p + 1, 8);  // lands with scan_kept's reads
+    scan_kept(e, K, n_ips_held, used, e->st_cap, E.ev[1], "internal: removal counts exceed the tables");
+    R.ips_found = found;
+    R.device_ms = E.ms(0, 1);
+    if (!selected) {  // the tables were only read
+      if (out) *out = R;
+      return BJX_OK;
+    }
+    e->counters_fresh = false;
+
+    // 3. the expiry's rebuild, with k_rm_st in k_exp_st's place
+    rebuild_kept(e, K, n_ips_held, used, E.ev[2], E.ev[3], "bjx_state_remove: no device memory for the new tables (state unchanged)",
+                 [&](NewTables &nw) {
+                   hipLaunchKernelGGL(k_rm_st, dim3(grid_for(e->st_cap)), dim3(kBlock), 0, st, e->st_cap, S.st, F, n_ips_held,
+                                      n_names, sel, K.nid, nw.st, nw.st_cap - 1);
+                 });
+    R.states_dropped = n_st - std::min<uint64_t>(n_st, K.states);
+    R.ips_dropped = n_ips_held - K.ips;
+    R.arena_bytes_after = K.bytes;
+    R.device_bytes_after = state_device_bytes(e->ip_cap, e->st_cap, S.arena_cap);
+    R.device_ms += E.ms(2, 3);
+    if (out) *out = R;
     return BJX_OK;
   });
 }

@@ -392,6 +392,27 @@ class Engine:
             rows.append((blob[r.ip_off:r.ip_off + r.ip_len], blob[r.name_off:r.name_off + r.name_len], r.hits, r.start_ns))
         return {"n_matched": out.n_matched, "n_ips_matched": out.n_ips_matched, "rows": rows, "device_ms": out.device_ms}
 
+    _remove = "bjx_state_remove"
+
+    def state_remove(self, ips=None, ip=None, name=None, min_hits: int = INT64_MIN, min_start_ns: int = INT64_MIN,
+                     max_start_ns: int = INT64_MAX) -> dict:
+        """Forget every state that passes the filter (state_query's ip, name,
+        min_hits, min_start_ns, max_start_ns) and, with `ips` (an iterable of
+        str / bytes; None or empty: no list, as n_ips == 0 in C), whose IP is listed; every IP left without
+        a state goes too (bjx_state_remove; banjax_amd/state_remove.py is its
+        model).  Nothing selected: the engine is left exactly as it was.
+        Returns the bjx_remove_stats fields."""
+        ipb = None if ip is None else _lib.b(ip)
+        nb = None if name is None else _lib.b(name)
+        f = _lib.StateFilter(_lib.Str(ipb, len(ipb or b"")), _lib.Str(nb, len(nb or b"")), min_hits, min_start_ns,
+                             max_start_ns, _lib.QUERY_BY_HITS, 0)
+        lst = [] if ips is None else [_lib.b(x) for x in ips]
+        arr = (_lib.Str * max(len(lst), 1))(*[_lib.Str(x, len(x)) for x in lst])
+        st = _lib.RemoveStats()
+        self._check(getattr(_lib.lib(), self._remove)(self._h, C.byref(f), arr if lst else None, len(lst), C.byref(st)),
+                    "state_remove")
+        return {k: getattr(st, k) for k, _ in _lib.RemoveStats._fields_}
+
     _rule_stats = "bjx_"
 
     def rule_stats(self, total: bool = False) -> dict:
@@ -557,6 +578,9 @@ class Node:
 
     _query = "bjx_node_state_query"
     state_query = Engine.state_query  # every shard's answer merged, IPs engine-major; an ip filter asks its owner only
+
+    _remove = "bjx_node_state_remove"
+    state_remove = Engine.state_remove  # every shard gets the filter and the whole list; stats summed
 
     _rule_stats = "bjx_node_"
     rule_stats = Engine.rule_stats  # the engines' arrays summed; engine(k).rule_stats() has engine k's own

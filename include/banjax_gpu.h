@@ -425,6 +425,60 @@ typedef struct bjx_state_rows {     /* 56 B */
   double device_ms;        /* HIP events, copies excluded */
 } bjx_state_rows;
 int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_state_rows *out);
+/* ---- Remove: forget chosen states.  The reference's host owns a Go map and
+   can delete from it; here the state lives in HBM, so the host asks.  Uses: an
+   unban (the reference's POST /unban, http_server.go:262-312, clears the
+   decision and leaves the IP's counters, often exactly at their threshold),
+   a rule whose rate or regex changed on reload (state is keyed by rule name
+   and survives it), a new allow-list entry, a false positive found with
+   bjx_state_query.
+
+   Selection: a state is dropped when it has valid != 0 and passes the five
+   conditions of *f exactly as bjx_state_query reads them (ip, name, min_hits,
+   min_start_ns, max_start_ns; order and limit are not read) and, when
+   n_ips > 0, its IP is one of ips[0..n_ips), compared by bytes.  The list and
+   the filter mean both: f->ip together with a list selects only when that IP
+   is in the list.  Duplicates in the list are allowed, a listed IP the engine
+   does not hold is not an error, a length-0 IP is a value.  Every IP left
+   without a state goes too.  A counts-only bjx_state_query with the same
+   filter previews a removal without a list: its n_matched is states_dropped.
+
+   Not errors (nothing is selected): a name the engine never interned, an
+   empty start window.  An all-pass filter without a list drops everything:
+   whatever a caller can observe then equals bjx_state_clear.
+   BJX_ERR_ARG: a NULL handle or f; n_ips > 0 with NULL ips; an entry (or
+   f->ip, f->name) with len > 0 and a NULL ptr; 2^32 list bytes or more in
+   total; a call between bjx_match_batch and its bjx_finish_batch* (the node
+   call waits for the node batch instead, as expiry does).  The new tables are
+   allocated before the old ones are freed: BJX_ERR_NOMEM leaves the state
+   untouched and usable.  out may be NULL.  Takes the engine lock like the
+   other bjx_state_* calls.
+
+   Afterwards everything observable equals an engine that imported a snapshot
+   of the surviving states: bjx_state_get / _len / _dump / _query / _export,
+   every later RuleResult (seen_ip, match_type, exceeded), trips and bans.
+   Surviving IPs keep their relative first-seen order and ids are dense again;
+   a removed IP that returns is a new IP, after them.  The tables are rebuilt
+   as bjx_state_expire rebuilds them, with its sizing rule (never below the
+   creation capacities, never above the present ones); rehashes does not count
+   a removal.  states_dropped is states_before minus the states kept, the
+   expiry's convention: a removal with max_start_ns = cutoff - 1 and everything
+   else open reports what bjx_state_expire(cutoff) reports and leaves the same
+   state.
+
+   When nothing is selected the engine is left exactly as it was: no rebuild
+   runs, no table changes size, and the stats' after equals their before
+   (unlike the expiry, which always rebuilds: an unban of an IP the engine does
+   not hold is the common case and must not move the tables). */
+typedef struct bjx_remove_stats {   /* 80 B */
+  uint64_t states_before, states_dropped;
+  uint64_t ips_before, ips_dropped;          /* IPs left without any state */
+  uint64_t ips_found;                        /* distinct listed IPs the engine held (0 without a list) */
+  uint64_t arena_bytes_before, arena_bytes_after;
+  uint64_t device_bytes_before, device_bytes_after;  /* as bjx_state_stats.device_bytes */
+  double device_ms;                          /* HIP events, copies excluded */
+} bjx_remove_stats;
+int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const bjx_str *ips, size_t n_ips, bjx_remove_stats *out);
 /* RegexRateLimitStates.String(): "ip:\n\trule:\n\t\t{hits start}\n" blocks, IPs in
    first-seen order.  Returns the full length (writes at most cap bytes). */
 size_t bjx_state_dump(bjx_engine *e, char *out, size_t cap);
@@ -643,6 +697,14 @@ int bjx_node_state_import(bjx_node *n, const uint8_t *snap, uint64_t len, bjx_sn
    bjx_node_state_expire does; rows and bytes are node-owned until the next
    query on the node. */
 int bjx_node_state_query(bjx_node *n, const bjx_state_filter *f, bjx_state_rows *out);
+/* bjx_state_remove over the node.  Every engine gets the same filter and the
+   whole list; an IP lives on one engine, so the sums are exact: counts and
+   bytes summed, device_ms the slowest shard's.  Waits for the node batch, as
+   bjx_node_state_expire does.  Every shard is asked even when one fails; the
+   first failure is returned, and the shards already done stay done.  Removal
+   is idempotent, so the caller repeats the call (the repeat's stats count
+   what it still found).  out may be NULL. */
+int bjx_node_state_remove(bjx_node *n, const bjx_state_filter *f, const bjx_str *ips, size_t n_ips, bjx_remove_stats *out);
 /* bjx_batch_rule_stats / bjx_rule_stats_total / bjx_rule_stats_reset over the
    node: the engines' arrays summed (engine k counted chunk k's lines),
    n_lines summed, device_ms the slowest engine's (totals: those summed). */
