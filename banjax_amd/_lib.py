@@ -261,6 +261,10 @@ def lib():
     L.bjx_debug_set_claim_budget.argtypes = [vp, C.c_uint64]
     L.bjx_debug_set_slot_cache.restype = C.c_int
     L.bjx_debug_set_slot_cache.argtypes = [vp, C.c_int]
+    L.bjx_debug_set_bucket_bits.restype = C.c_int
+    L.bjx_debug_set_bucket_bits.argtypes = [vp, C.c_uint32]
+    L.bjx_debug_state_slots.restype = C.c_int
+    L.bjx_debug_state_slots.argtypes = [vp, vp, vp, C.POINTER(Str), sz, vp, sz, vp]
     L.bjx_debug_set_ip_hash_mask.restype = C.c_int
     L.bjx_debug_set_ip_hash_mask.argtypes = [vp, C.c_uint64]
     L.bjx_debug_set_dfa_state_cap.restype = C.c_int

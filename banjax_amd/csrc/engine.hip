@@ -5117,6 +5117,7 @@ struct bjx_engine {
   uint32_t lines2_lds = 0;     // dynamic LDS k_lines2 was last configured for
   uint32_t lines2_w = 0;       // ... and the instance (mask width) it was set on
   int dbg_slot_cache = -1;     // bjx_debug_set_slot_cache: -1 = BJX_SLOT_CACHE / default on, 0 off, 1 on
+  uint32_t dbg_bucket_bits = 0;  // bjx_debug_set_bucket_bits: 0 = kBucketBits, else the grouping's high slot bits
   uint64_t host_counters[3] = {0, 0, 0};
   // host_counters were read with the match phase's last counts, nothing has
   // touched the tables since (run_batch: match, then straight to the rate limit)
@@ -6879,7 +6880,9 @@ static void rl_sort_apply(bjx_engine *e, const Bind &B, const EvSrc &E, uint64_t
   const Rec *rec2 = reinterpret_cast<const Rec *>(e->ev_rec2.p);
   const bool check = getenv("BJX_CHECK") != nullptr;
   const int bits = std::max(1, bit_width(e->st_cap - 1));
-  const int L = bits - kBucketBits;
+  // (bjx_debug_set_bucket_bits: a test reaches every L with the default table)
+  const int bucket_bits = e->dbg_bucket_bits ? (int)e->dbg_bucket_bits : kBucketBits;
+  const int L = bits - bucket_bits;
   // BJX_SORT2 (test / timing hook, read per batch): 0 the full sort always,
   // 2 two-level whenever the table allows it (no batch-size gate, no hold)
   const char *s2 = getenv("BJX_SORT2");
@@ -6891,7 +6894,7 @@ static void rl_sort_apply(bjx_engine *e, const Bind &B, const EvSrc &E, uint64_t
   // two-level grouping (k_bucket_apply) unless the buckets would be too full on
   // average (then most of them would take the full path anyway); BJX_CHECK's
   // write accounting covers both paths
-  const uint32_t nb = 1u << kBucketBits;
+  const uint32_t nb = 1u << bucket_bits;
   // a batch whose oversized buckets held more than 1/8 of its events (a hot
   // key) is followed by kSort2Hold batches on the full sort: the events of those
   // buckets pay for a gather and a sort of their own on top of the two passes
@@ -8406,6 +8409,54 @@ extern "C" int bjx_debug_set_slot_cache(bjx_engine *e, int on) {
   e->dbg_slot_cache = on < 0 ? -1 : on != 0;
   e->bound_uid = 0;  // the next batch re-binds and applies it
   return BJX_OK;
+}
+extern "C" int bjx_debug_set_bucket_bits(bjx_engine *e, uint32_t bits) {
+  if (!e || bits > (uint32_t)kBucketBits) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->dbg_bucket_bits = bits;
+  return BJX_OK;
+}
+extern "C" int bjx_debug_state_slots(bjx_engine *e, const uint8_t *ip_bytes, const uint32_t *ip_off, const bjx_str *names,
+                                     size_t n_names, const uint32_t *name_idx, size_t n, int64_t *slots) {
+  if (!e) return BJX_ERR_ARG;
+  if (!n) return BJX_OK;
+  if (!ip_off || !name_idx || !slots || !names || !n_names || n > 0x7FFFFFFFull || ip_off[0] != 0 || (ip_off[n] && !ip_bytes))
+    return BJX_ERR_ARG;
+  for (size_t k = 0; k < n; ++k)
+    if (ip_off[k + 1] < ip_off[k] || name_idx[k] >= n_names) return BJX_ERR_ARG;
+  for (size_t k = 0; k < n_names; ++k)
+    if (names[k].len && !names[k].ptr) return BJX_ERR_ARG;
+  return guarded(e, [&]() -> int {
+    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_debug_state_slots between bjx_match_batch and its bjx_finish_batch");
+    // name ids as interned (kNone: a name no ruleset of this engine has used, so no state has it)
+    std::vector<uint32_t> ids(n_names, kNone);
+    for (size_t k = 0; k < n_names; ++k) {
+      auto it = e->name_ids.find(std::string(names[k].ptr ? names[k].ptr : "", names[k].len));
+      if (it != e->name_ids.end()) ids[k] = it->second;
+    }
+    // one image, as bjx_state_remove's list: u32 off[n + 1], u32 name id[n], then the bytes
+    // (4 readable bytes past them for hash_bytes' word loads)
+    const uint64_t off_bytes = ((uint64_t)n + 1) * 4, id_bytes = (uint64_t)n * 4, total = ip_off[n];
+    const uint64_t img_bytes = off_bytes + id_bytes + total;
+    std::vector<uint8_t> img(img_bytes);
+    memcpy(img.data(), ip_off, off_bytes);
+    uint32_t *pid = reinterpret_cast<uint32_t *>(img.data() + off_bytes);
+    for (size_t k = 0; k < n; ++k) pid[k] = ids[name_idx[k]];
+    if (total) memcpy(img.data() + off_bytes + id_bytes, ip_bytes, total);
+    ExpAlloc tmp;
+    uint8_t *d_img = tmp.get<uint8_t>(((img_bytes + 3) & ~3ull) + 16);
+    int64_t *d_out = tmp.get<int64_t>(n);
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_debug_state_slots: no device memory for the list");
+    snap_copy_in(e, d_img, img.data(), img_bytes);  // one upload; waits for the stream
+    read_counters(e);
+    hipLaunchKernelGGL(k_state_slots, dim3(grid_for(n)), dim3(kBlock), 0, e->stream, e->S, e->dbg_hash_mask, (uint64_t)n,
+                       e->host_counters[0], reinterpret_cast<const uint32_t *>(d_img),
+                       reinterpret_cast<const uint32_t *>(d_img + off_bytes), d_img + off_bytes + id_bytes, d_out);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(slots, d_out, n * 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    return BJX_OK;
+  });
 }
 extern "C" int bjx_debug_set_rule_stats_lds(bjx_engine *e, uint32_t max_rules) {
   if (!e) return BJX_ERR_ARG;

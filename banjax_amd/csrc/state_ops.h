@@ -676,6 +676,42 @@ __global__ void k_state_get(State S, uint64_t h, const uint8_t *ip, uint32_t len
   }
 }
 
+// bjx_debug_state_slots: k_state_get's lookup for a whole list, one lane per
+// (ip, name id) pair of the packed list (entry i: bytes[off[i], off[i + 1]),
+// 4 readable bytes past the last one for hash_bytes' word loads); out[i] = the
+// state-table slot (k_state_get's j) of a live state, -1 where it finds none
+__global__ __launch_bounds__(kBlock) void k_state_slots(State S, uint64_t hmask, uint64_t n, uint64_t n_ips,
+                                                        const uint32_t *__restrict__ off, const uint32_t *__restrict__ name_id,
+                                                        const uint8_t *__restrict__ bytes, int64_t *__restrict__ out) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  int64_t slot = -1;
+  const uint32_t a = off[t], len = off[t + 1] - a, name = name_id[t];
+  const uint8_t *src = bytes + a;
+  uint64_t h = hash_bytes(src, len);
+  if (hmask) h = (h & hmask) | 1ull;
+  uint64_t i = h & S.ip_mask;
+  for (uint64_t step = 0; step <= S.ip_mask && name != kNone; ++step, i = (i + 1) & S.ip_mask) {
+    const uint64_t cur = S.ip[i].hash;
+    if (cur == 0) break;
+    if (cur != h) continue;
+    const uint32_t id = S.ip[i].id;
+    if (id >= n_ips || S.ip_len[id] != len || !bytes_eq(S.arena + S.ip_off[id], src, len)) continue;
+    const uint64_t key = ((uint64_t)(id + 1) << 24) | name;
+    uint64_t j = mix64(key) & S.st_mask;
+    for (uint64_t s2 = 0; s2 <= S.st_mask; ++s2, j = (j + 1) & S.st_mask) {
+      const uint64_t k = S.st[j].key;
+      if (k == 0) break;
+      if (k == key) {
+        if (S.st[j].valid) slot = (int64_t)j;
+        break;
+      }
+    }
+    break;
+  }
+  out[t] = slot;
+}
+
 // live keys left in the state / IP tables (bjx_state_clear's check)
 __global__ void k_count_live(const StSlot *__restrict__ st, uint64_t st_cap, const IpSlot *__restrict__ ip, uint64_t ip_cap,
                              unsigned long long *__restrict__ cnt) {

@@ -315,6 +315,36 @@ class Engine:
         """Test hook: state-slot cache on (1), off (0), default (-1), from the next batch."""
         self._check(_lib.lib().bjx_debug_set_slot_cache(self._h, on), "debug_set_slot_cache")
 
+    def debug_set_bucket_bits(self, bits: int):
+        """Test hook: the two-level rate-limit grouping uses `bits` high slot
+        bits (1..16; 0 = the default 16), from the next batch."""
+        self._check(_lib.lib().bjx_debug_set_bucket_bits(self._h, bits), "debug_set_bucket_bits")
+
+    def debug_state_slots(self, ips, names):
+        """Test hook: the state-table slot of each (ips[k], names[k]) state, -1
+        where there is none, as a numpy int64 array; one launch for the whole
+        list (bjx_debug_state_slots).  The engine is unchanged."""
+        import numpy as np
+        ipb = [_lib.b(x) for x in ips]
+        nmb = [_lib.b(x) for x in names]
+        assert len(ipb) == len(nmb)
+        n = len(ipb)
+        out = np.full(n, -1, dtype=np.int64)
+        if not n:
+            return out
+        off = np.zeros(n + 1, dtype=np.uint32)
+        total = np.cumsum(np.fromiter((len(x) for x in ipb), dtype=np.uint64, count=n))
+        assert int(total[-1]) < 1 << 32
+        off[1:] = total
+        blob = np.frombuffer(b"".join(ipb) + b"\0", dtype=np.uint8)
+        table = sorted(set(nmb))
+        where = {x: k for k, x in enumerate(table)}
+        idx = np.fromiter((where[x] for x in nmb), dtype=np.uint32, count=n)
+        arr = (_lib.Str * len(table))(*[_lib.Str(x, len(x)) for x in table])
+        self._check(_lib.lib().bjx_debug_state_slots(self._h, blob.ctypes.data, off.ctypes.data, arr, len(table),
+                                                     idx.ctypes.data, n, out.ctypes.data), "debug_state_slots")
+        return out
+
     def state_clear(self):
         self._check(_lib.lib().bjx_state_clear(self._h), "state_clear")
 

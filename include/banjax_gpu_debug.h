@@ -61,6 +61,25 @@ int bjx_debug_set_claim_budget(bjx_engine *e, uint64_t max_new);
 /* Test hook: the per-IP state-slot cache of k_st_claim on (1), off (0) or as
    BJX_SLOT_CACHE / the default says (-1), from the next batch on. */
 int bjx_debug_set_slot_cache(bjx_engine *e, int on);
+/* Test hook (host side): the two-level grouping of the rate-limit stage uses
+   `bits` high state-slot bits, from the next batch on: 2^bits buckets of
+   2^L slots, L = log2(state slots) - bits.  0 = the default 16; 1..16 are
+   accepted, anything else is BJX_ERR_ARG.  The grouping still needs
+   0 < L <= 15 (otherwise the full sort runs and scan_stats' grouping is 0), so
+   with the default 2^22-slot table bits 16..7 give L = 6..15: every L
+   k_bucket_apply can run at without a table of 2^(16 + L) slots.  Unused, the
+   same kernels run with the same arguments as without the hook. */
+int bjx_debug_set_bucket_bits(bjx_engine *e, uint32_t bits);
+/* Test hook: the state-table slot index each of n (IP, rule name) states
+   occupies, found as bjx_state_get finds it (hash, probe chain, IP bytes,
+   then the state's key), in one launch for the whole list; -1 where there is
+   no such state.  IP k is ip_bytes[ip_off[k], ip_off[k + 1]) (ip_off has
+   n + 1 entries and starts at 0; the packed list of bjx_state_remove), its
+   name is names[name_idx[k]].  Writes nothing in the engine.  A state keeps
+   its slot until the tables are rebuilt (growth, expire, remove, import,
+   clear): bjx_state_stats' state_slots and rehashes tell. */
+int bjx_debug_state_slots(bjx_engine *e, const uint8_t *ip_bytes, const uint32_t *ip_off, const bjx_str *names,
+                          size_t n_names, const uint32_t *name_idx, size_t n, int64_t *slots);
 /* Test hook: rules compiled afterwards use the bit-parallel NFA once their DFA
    passes `cap` states (0 = default 4096; 1 = every rule that fits the NFA),
    process-wide; clears the compiled-pattern cache. */
