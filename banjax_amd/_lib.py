@@ -112,6 +112,7 @@ EXPORTS = [
     "bjx_node_state_export_bound", "bjx_node_state_export", "bjx_node_state_import",
     "bjx_state_query", "bjx_node_state_query",
     "bjx_state_remove", "bjx_node_state_remove",
+    "bjx_state_query_nets", "bjx_node_state_query_nets", "bjx_state_remove_nets", "bjx_node_state_remove_nets",
     "bjx_batch_rule_stats", "bjx_rule_stats_total", "bjx_rule_stats_reset",
     "bjx_node_batch_rule_stats", "bjx_node_rule_stats_total", "bjx_node_rule_stats_reset",
 ]
@@ -136,6 +137,7 @@ class SnapshotStats(C.Structure):
 
 
 QUERY_BY_HITS, QUERY_BY_START, QUERY_MAX_ROWS = 0, 1, 65536
+NETS_MAX = 65536
 
 
 class StateFilter(C.Structure):
@@ -335,6 +337,13 @@ def lib():
         f = getattr(L, name)
         f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(StateRows)]
     for name in ("bjx_state_remove", "bjx_node_state_remove"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(Str), sz, C.POINTER(RemoveStats)]
+    for name in ("bjx_state_query_nets", "bjx_node_state_query_nets"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(Str), sz, C.POINTER(StateRows),
+                                          C.POINTER(C.POINTER(C.c_uint64))]
+    for name in ("bjx_state_remove_nets", "bjx_node_state_remove_nets"):
         f = getattr(L, name)
         f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(Str), sz, C.POINTER(RemoveStats)]
     for pre in ("bjx_", "bjx_node_"):

@@ -47,6 +47,7 @@
 #include "snapshot.h"
 #include "state_query.h"
 #include "state_remove.h"
+#include "state_nets.h"
 
 using namespace bjx;
 
@@ -5234,6 +5235,7 @@ struct bjx_engine {
   HostBuf<uint8_t> snap_pin;  // bjx_state_export / bjx_state_import: two pinned chunks the blob moves through
   HostBuf<bjx_state_row> qry_rows;  // bjx_state_query: the last answer (valid until the next query)
   HostBuf<uint8_t> qry_bytes;
+  std::vector<uint64_t> qry_net_ips;  // bjx_state_query_nets: the last answer's net_ips
 
   // per-rule counts of the batches closed with BJX_RULE_STATS (rule_stats.h);
   // nothing here is allocated or created before the first such batch

@@ -46,6 +46,7 @@
 #include "snapshot.h"
 #include "state_query.h"
 #include "state_remove.h"
+#include "state_nets.h"
 
 namespace {
 
@@ -127,6 +128,7 @@ struct bjx_node {
   // the last bjx_node_state_query's merged answer
   std::vector<bjx_state_row> q_rows;
   std::vector<uint8_t> q_bytes;
+  std::vector<uint64_t> q_net_ips;  // and of the last bjx_node_state_query_nets, the summed net_ips
   // per-rule counts (BJX_RULE_STATS): the engines' arrays summed, for the last
   // batch and over every flagged batch since its ruleset came into use
   bool rs_counted = false;
@@ -1070,6 +1072,63 @@ extern "C" int bjx_node_state_remove(bjx_node *n, const bjx_state_filter *f, con
       bjx_engine *e = n->parts[k].e;
       bjx_remove_stats s{};
       const int rc = bjx_state_remove(e, f, ips, n_ips, &s);
+      if (rc != BJX_OK) {
+        if (first_rc == BJX_OK) {
+          first_rc = rc;
+          first_msg = "engine " + std::to_string(k) + ": " + bjx_engine_last_error(e);
+        }
+        continue;
+      }
+      bjx_remove::add(&t, s);
+    }
+    if (first_rc != BJX_OK) fail(first_rc, first_msg);
+    if (out) *out = t;
+    return BJX_OK;
+  });
+}
+
+// every shard with the same filter and nets (with an ip filter too: the shards
+// that do not hold it answer nothing); rows merged as bjx_node_state_query's,
+// net_ips summed entry by entry (state_nets.h)
+extern "C" int bjx_node_state_query_nets(bjx_node *n, const bjx_state_filter *f, const bjx_str *nets, size_t n_nets,
+                                         bjx_state_rows *out, const uint64_t **net_ips) {
+  if (!n || !f || !out) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    memset(out, 0, sizeof *out);
+    if (net_ips) *net_ips = nullptr;
+    if (const char *why = bjx_query::check_filter(f)) fail(BJX_ERR_ARG, std::string("bjx_node_state_query_nets: ") + why);
+    if (const char *why = bjx_nets::check_args(f, nets, n_nets)) fail(BJX_ERR_ARG, std::string("bjx_node_state_query_nets: ") + why);
+    std::vector<bjx_state_rows> ans;
+    std::vector<uint64_t> sum;
+    for (size_t k = 0; k < n->parts.size(); ++k) {
+      bjx_engine *e = n->parts[k].e;
+      bjx_state_rows a{};
+      const uint64_t *ni = nullptr;
+      const int rc = bjx_state_query_nets(e, f, nets, n_nets, &a, &ni);
+      if (rc != BJX_OK) fail(rc, "engine " + std::to_string(k) + ": " + bjx_engine_last_error(e));
+      ans.push_back(a);
+      bjx_nets::add(&sum, ni, n_nets);
+    }
+    bjx_query::merge(ans, f->order, f->limit, out, &n->q_rows, &n->q_bytes);
+    n->q_net_ips.swap(sum);
+    if (net_ips) *net_ips = n->q_net_ips.data();
+    return BJX_OK;
+  });
+}
+
+// as bjx_node_state_remove: every shard is asked, the first failure returned
+extern "C" int bjx_node_state_remove_nets(bjx_node *n, const bjx_state_filter *f, const bjx_str *nets, size_t n_nets,
+                                          bjx_remove_stats *out) {
+  if (!n) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    if (const char *why = bjx_nets::check_args(f, nets, n_nets)) fail(BJX_ERR_ARG, std::string("bjx_node_state_remove_nets: ") + why);
+    bjx_remove_stats t{};
+    int first_rc = BJX_OK;
+    std::string first_msg;
+    for (size_t k = 0; k < n->parts.size(); ++k) {
+      bjx_engine *e = n->parts[k].e;
+      bjx_remove_stats s{};
+      const int rc = bjx_state_remove_nets(e, f, nets, n_nets, &s);
       if (rc != BJX_OK) {
         if (first_rc == BJX_OK) {
           first_rc = rc;

@@ -252,11 +252,13 @@ __device__ __forceinline__ ulonglong2 q_cand(const StSlot &v, const QFilter &F, 
                          (((v.key >> 24) - 1) << 24) | rank[v.key & 0xFFFFFFull]);
 }
 // grid-stride; cnt[0] += passing states (one atomic per block), keep[ip id] = 1;
-// room != 0: the candidates appended at cnt[1]
+// room != 0: the candidates appended at cnt[1].  sel != NULL (a nets query): a
+// state passes only when sel[its IP id] is set, as rm_selected reads it
 __global__ __launch_bounds__(kBlock) void k_qry_scan(uint64_t st_cap, const StSlot *__restrict__ st, QFilter F, uint64_t n_ips,
                                                      uint32_t n_names, const uint32_t *__restrict__ rank,
-                                                     uint32_t *__restrict__ keep, unsigned long long *__restrict__ cnt,
-                                                     uint64_t room, ulonglong2 *__restrict__ cand) {
+                                                     const uint32_t *__restrict__ sel, uint32_t *__restrict__ keep,
+                                                     unsigned long long *__restrict__ cnt, uint64_t room,
+                                                     ulonglong2 *__restrict__ cand) {
   uint64_t n = 0, z = 0;
   constexpr uint64_t kTile = (uint64_t)kBlock * kQryItems;  // slots per block and pass: one block_alloc for all of them
   for (uint64_t base = (uint64_t)blockIdx.x * kTile; base < st_cap; base += (uint64_t)gridDim.x * kTile) {
@@ -268,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void k_qry_scan(uint64_t st_cap, const StSl
       c[j] = make_ulonglong2(0, 0);
       if (i >= st_cap) continue;
       const StSlot v = st[i];
-      if (!q_pass(v, F, n_ips, n_names)) continue;
+      if (!q_pass(v, F, n_ips, n_names) || (sel && !sel[(v.key >> 24) - 1])) continue;
       keep[(v.key >> 24) - 1] = 1u;  // every writer stores the same value
       if (room) c[j] = q_cand(v, F, rank);
       mask |= 1u << j;
@@ -523,6 +525,87 @@ __global__ void k_rm_st(uint64_t old_cap, const StSlot *__restrict__ o, QFilter 
   const uint64_t key = ((uint64_t)(nid[(v.key >> 24) - 1] + 1) << 24) | (v.key & 0xFFFFFFull);
   fresh_put_st(nt, nmask, key, v.hits, v.start, v.valid);
 }
+
+// selection by network (bjx_state_query_nets / bjx_state_remove_nets; the
+// argument checks, the net table and the membership rule: state_nets.h).  One
+// lane per held IP: its bytes are read in place from the arena (byte loads, no
+// alignment and no length assumed: go_parse_addr reads [0, len) and nothing
+// else) and parsed as check_is_allowed parses a line's IP; bjx_nets::member
+// then runs one binary search per prefix length of the address's family over
+// the table in global memory (1 MiB at BJX_NETS_MAX entries, L2-resident).
+// An id past n_ips or bytes past arena_used cannot come from a finished batch
+// and select nothing.
+__device__ __forceinline__ bool net_ip_addr(uint64_t id, const uint64_t *__restrict__ ip_off, const uint32_t *__restrict__ ip_len,
+                                            const uint8_t *__restrict__ arena, uint64_t arena_used, uint8_t a[16]) {
+  const uint64_t so = ip_off[id];
+  const uint32_t len = ip_len[id];
+  if (so > arena_used || len > arena_used - so) return false;
+  bool is4;
+  return go_parse_addr(arena + so, len, a, &is4);
+}
+// grid-stride; sel[id] = 1 when a network holds IP id (sel[] zeroed before),
+// cnt[0] += those IPs (one atomic per block)
+__global__ __launch_bounds__(kBlock) void k_net_sel(uint64_t n_ips, const uint64_t *__restrict__ ip_off,
+                                                    const uint32_t *__restrict__ ip_len, const uint8_t *__restrict__ arena,
+                                                    uint64_t arena_used, bjx_nets::View V, uint32_t *__restrict__ sel,
+                                                    unsigned long long *__restrict__ cnt) {
+  uint64_t n = 0, z = 0;
+  for (uint64_t id = (uint64_t)blockIdx.x * kBlock + threadIdx.x; id < n_ips; id += (uint64_t)gridDim.x * kBlock) {
+    uint8_t a[16];
+    if (!net_ip_addr(id, ip_off, ip_len, arena, arena_used, a)) continue;
+    if (bjx_nets::member(V, a, [](uint32_t) { return true; })) {
+      sel[id] = 1u;
+      ++n;
+    }
+  }
+  block_sum2(n, z);
+  if (threadIdx.x == 0 && n) atomicAdd(&cnt[0], (unsigned long long)n);
+}
+// after the state scan: every IP with a selected state (keep[id], which the
+// scan sets only where sel[id] is set) adds 1 to each canonical network that
+// holds it (cnt[] has n_canon counters, zeroed before).  A wide network holds
+// a large share of the IPs, and one global atomic per IP on its counter runs
+// at the rate of one address; so a block counts in LDS first -- an
+// open-addressed table of kNetLds (network, count) slots, claimed by CAS --
+// over all the IPs it walks (few blocks, grid-stride) and adds each slot to the
+// global counter once at the end.  A network that finds no slot within
+// kNetProbe steps (more distinct networks in one block than the table holds:
+// narrow ones, each with few IPs) is counted in global memory directly.
+constexpr uint32_t kNetLds = 2048, kNetProbe = 16;
+constexpr uint64_t kNetCountIps = 4096;  // held IPs per block of k_net_count (the grid is sized by it)
+__global__ __launch_bounds__(kBlock) void k_net_count(uint64_t n_ips, const uint32_t *__restrict__ keep,
+                                                      const uint64_t *__restrict__ ip_off, const uint32_t *__restrict__ ip_len,
+                                                      const uint8_t *__restrict__ arena, uint64_t arena_used, bjx_nets::View V,
+                                                      uint32_t n_canon, uint32_t *__restrict__ cnt) {
+  __shared__ uint32_t s_key[kNetLds], s_cnt[kNetLds];
+  for (uint32_t k = threadIdx.x; k < kNetLds; k += kBlock) {
+    s_key[k] = kNone;
+    s_cnt[k] = 0;
+  }
+  __syncthreads();
+  for (uint64_t id = (uint64_t)blockIdx.x * kBlock + threadIdx.x; id < n_ips; id += (uint64_t)gridDim.x * kBlock) {
+    if (!keep[id]) continue;
+    uint8_t a[16];
+    if (!net_ip_addr(id, ip_off, ip_len, arena, arena_used, a)) continue;
+    bjx_nets::member(V, a, [&](uint32_t c) {
+      if (c >= n_canon) return false;
+      uint32_t h = (c * 2654435761u) >> 21;  // 11 bits: kNetLds slots
+      for (uint32_t step = 0; step < kNetProbe; ++step, h = (h + 1) & (kNetLds - 1)) {
+        const uint32_t was = atomicCAS(&s_key[h], kNone, c);
+        if (was == kNone || was == c) {
+          atomicAdd(&s_cnt[h], 1u);
+          return false;
+        }
+      }
+      atomicAdd(&cnt[c], 1u);
+      return false;
+    });
+  }
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < kNetLds; k += kBlock)
+    if (s_key[k] != kNone && s_cnt[k]) atomicAdd(&cnt[s_key[k]], s_cnt[k]);
+}
+static_assert(kNetLds == 1u << 11, "k_net_count hashes to 11 bits");
 
 // snapshot import (bjx_state_import).  err[c] = 1 (plain stores of one value)
 // when check c fails: 1 ip_off not monotone from 0, 2 ip_off[n_ips] !=
@@ -1163,13 +1246,26 @@ extern "C" int bjx_state_expire(bjx_engine *e, int64_t cutoff_ns, bjx_expire_sta
 // selected, and when any state is selected the expiry's rebuild follows with
 // k_rm_st in k_exp_st's place.  Nothing selected: the tables were only read and
 // stay as they are.
-extern "C" int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const bjx_str *ips, size_t n_ips,
-                                bjx_remove_stats *out) {
+//
+// With nets (bjx_state_remove_nets) k_net_sel sets sel[] in k_rm_ips' place:
+// every held IP a network holds.  A filter ip is tested against the table on
+// the host and, when a network holds it, looked up as the list form's.
+static int state_remove_impl(bjx_engine *e, const bjx_state_filter *f, const bjx_str *ips, size_t n_ips, const bjx_str *nets,
+                             size_t n_nets, bool by_nets, bjx_remove_stats *out) {
+  const std::string who = by_nets ? "bjx_state_remove_nets" : "bjx_state_remove";
   return guarded(e, [&]() -> int {
-    if (const char *why = bjx_remove::check_args(f, ips, n_ips)) throw BjxError(BJX_ERR_ARG, std::string("bjx_state_remove: ") + why);
-    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_remove between bjx_match_batch and its bjx_finish_batch");
+    bjx_nets::Table T;
+    if (by_nets) {
+      if (const char *why = bjx_nets::check_args(f, nets, n_nets)) throw BjxError(BJX_ERR_ARG, who + ": " + why);
+      const int64_t bad = bjx_nets::build(nets, n_nets, &T);
+      if (bad >= 0) throw BjxError(BJX_ERR_ARG, who + ": " + bjx_nets::bad_entry(bad));
+    } else if (const char *why = bjx_remove::check_args(f, ips, n_ips)) {
+      throw BjxError(BJX_ERR_ARG, who + ": " + why);
+    }
+    if (e->batch_open) throw BjxError(BJX_ERR_ARG, who + " between bjx_match_batch and its bjx_finish_batch");
     bjx_remove::List L;
-    bjx_remove::pack(*f, ips, n_ips, &L);
+    bjx_remove::pack(*f, by_nets ? nullptr : ips, by_nets ? 0 : n_ips, &L);
+    if (by_nets && L.has_ip && !T.holds(reinterpret_cast<const uint8_t *>(f->ip.ptr), (uint32_t)f->ip.len)) L.nothing = true;
     HIP_OK(hipDeviceSynchronize());  // nothing of an earlier batch may land after the rebuild
     State &S = e->S;
     hipStream_t st = e->stream;
@@ -1193,7 +1289,7 @@ extern "C" int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const 
       if (it == e->name_ids.end()) nothing = true;
       else F.name = it->second;
     }
-    const bool count_found = L.n_list != 0 && n_ips_held != 0;  // ips_found is asked for
+    const bool count_found = (by_nets || L.n_list != 0) && n_ips_held != 0;  // ips_found is asked for
     if (nothing && !count_found) {
       if (out) *out = R;
       return BJX_OK;
@@ -1201,13 +1297,20 @@ extern "C" int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const 
 
     ExpAlloc tmp;
     Kept K(tmp, n_ips_held);
-    uint32_t *sel = L.restrict ? tmp.get<uint32_t>(n_ips_held + 1) : nullptr;
+    uint32_t *sel = L.restrict || by_nets ? tmp.get<uint32_t>(n_ips_held + 1) : nullptr;
     uint32_t *d_sum = tmp.get<uint32_t>(4);
+    // the net table on the device: one image (state_nets.h)
+    std::vector<uint8_t> net_img;
+    uint64_t o_dir = 0, o_k4 = 0;
+    const uint64_t net_bytes = by_nets ? T.image(&net_img, &o_dir, &o_k4) : 0;
+    uint8_t *d_net = by_nets ? tmp.get<uint8_t>(net_bytes + 16) : nullptr;
+    unsigned long long *d_found = by_nets ? tmp.get<unsigned long long>(2) : nullptr;
     // the list on the device: u32 off[entries + 1], then the bytes (word aligned, 4 readable bytes past them)
     const uint64_t off_bytes = ((uint64_t)L.n_entries() + 1) * 4;
     const uint64_t list_bytes = L.restrict ? off_bytes + L.bytes.size() : 0;
     uint8_t *d_list = L.restrict ? tmp.get<uint8_t>(((list_bytes + 3) & ~3ull) + 16) : nullptr;
-    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_remove: no device memory for the scan buffers");
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, who + ": no device memory for the scan buffers");
+    if (by_nets) snap_copy_in(e, d_net, net_img.data(), net_bytes);
     if (L.restrict) {
       std::vector<uint8_t> img(list_bytes);
       memcpy(img.data(), L.off.data(), off_bytes);
@@ -1230,7 +1333,19 @@ extern "C" int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const 
     uint32_t found = 0;
     HIP_OK(hipEventRecord(E.ev[0], st));
     HIP_OK(hipMemsetAsync(e->chk.p, 0, 16, st));
-    if (count_found) {
+    unsigned long long found_nets = 0;
+    if (count_found && by_nets) {
+      bjx_nets::View V = T.view();
+      V.k6 = reinterpret_cast<const uint64_t *>(d_net);
+      V.dir = reinterpret_cast<const bjx_nets::Dir *>(d_net + o_dir);
+      V.k4 = reinterpret_cast<const uint32_t *>(d_net + o_k4);
+      HIP_OK(hipMemsetAsync(d_found, 0, 16, st));
+      HIP_OK(hipMemsetAsync(sel, 0, (n_ips_held + 1) * 4, st));
+      hipLaunchKernelGGL(k_net_sel, dim3((unsigned)std::min<uint64_t>(grid_for(n_ips_held), 8192)), dim3(kBlock), 0, st, n_ips_held,
+                         S.ip_off, S.ip_len, S.arena, used, V, sel, d_found);
+      HIP_OK(hipGetLastError());
+      pin_get(e, &found_nets, d_found, 8);
+    } else if (count_found) {
       HIP_OK(hipMemsetAsync(d_sum, 0, 16, st));
       find_ips(0, L.n_list);
       cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceReduce::Sum(t, b, sel, d_sum, (int)n_ips_held, st); });
@@ -1239,7 +1354,7 @@ extern "C" int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const 
     if (nothing) {
       HIP_OK(hipEventRecord(E.ev[1], st));
       pin_sync(e);
-      R.ips_found = found;
+      R.ips_found = by_nets ? found_nets : found;
       R.device_ms = E.ms(0, 1);
       if (out) *out = R;
       return BJX_OK;
@@ -1256,7 +1371,7 @@ extern "C" int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const 
     HIP_OK(hipGetLastError());
     pin_get(e, &selected, e->chk.p + 1, 8);  // lands with scan_kept's reads
     scan_kept(e, K, n_ips_held, used, e->st_cap, E.ev[1], "internal: removal counts exceed the tables");
-    R.ips_found = found;
+    R.ips_found = by_nets ? found_nets : found;
     R.device_ms = E.ms(0, 1);
     if (!selected) {  // the tables were only read
       if (out) *out = R;
@@ -1265,7 +1380,8 @@ extern "C" int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const 
     e->counters_fresh = false;
 
     // 3. the expiry's rebuild, with k_rm_st in k_exp_st's place
-    rebuild_kept(e, K, n_ips_held, used, E.ev[2], E.ev[3], "bjx_state_remove: no device memory for the new tables (state unchanged)",
+    const std::string nomem = who + ": no device memory for the new tables (state unchanged)";
+    rebuild_kept(e, K, n_ips_held, used, E.ev[2], E.ev[3], nomem.c_str(),
                  [&](NewTables &nw) {
                    hipLaunchKernelGGL(k_rm_st, dim3(grid_for(e->st_cap)), dim3(kBlock), 0, st, e->st_cap, S.st, F, n_ips_held,
                                       n_names, sel, K.nid, nw.st, nw.st_cap - 1);
@@ -1278,6 +1394,16 @@ extern "C" int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const 
     if (out) *out = R;
     return BJX_OK;
   });
+}
+
+extern "C" int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const bjx_str *ips, size_t n_ips,
+                                bjx_remove_stats *out) {
+  return state_remove_impl(e, f, ips, n_ips, nullptr, 0, false, out);
+}
+
+extern "C" int bjx_state_remove_nets(bjx_engine *e, const bjx_state_filter *f, const bjx_str *nets, size_t n_nets,
+                                     bjx_remove_stats *out) {
+  return state_remove_impl(e, f, nullptr, 0, nets, n_nets, true, out);
 }
 
 extern "C" uint64_t bjx_state_export_bound(bjx_engine *e) {
@@ -1527,12 +1653,31 @@ extern "C" int bjx_state_import(bjx_engine *e, const uint8_t *snap, uint64_t len
 // which is sorted; the rows and their bytes are gathered on the device and
 // copied out.  The tables are only read.  The candidate buffer is sized by the
 // `states` counter (the most a scan can append).
-extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_state_rows *out) {
+//
+// With nets (bjx_state_query_nets) k_net_sel marks the held IPs a network
+// holds before the scan, which then passes only their states, and k_net_count
+// adds every IP with a passing state to the networks that hold it.  With an ip
+// filter the host tests that one IP against the table and the k_qry_ip path
+// runs as it is, or nothing does.
+static int state_query_impl(bjx_engine *e, const bjx_state_filter *f, const bjx_str *nets, size_t n_nets, bool by_nets,
+                            bjx_state_rows *out, const uint64_t **net_ips) {
   if (!e || !f || !out) return BJX_ERR_ARG;
+  const std::string who = by_nets ? "bjx_state_query_nets" : "bjx_state_query";
   return guarded(e, [&]() -> int {
     memset(out, 0, sizeof *out);
-    if (const char *why = bjx_query::check_filter(f)) throw BjxError(BJX_ERR_ARG, std::string("bjx_state_query: ") + why);
-    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_query between bjx_match_batch and its bjx_finish_batch");
+    if (net_ips) *net_ips = nullptr;
+    if (const char *why = bjx_query::check_filter(f)) throw BjxError(BJX_ERR_ARG, who + ": " + why);
+    bjx_nets::Table T;
+    if (by_nets) {
+      if (const char *why = bjx_nets::check_args(f, nets, n_nets)) throw BjxError(BJX_ERR_ARG, who + ": " + why);
+      const int64_t bad = bjx_nets::build(nets, n_nets, &T);
+      if (bad >= 0) throw BjxError(BJX_ERR_ARG, who + ": " + bjx_nets::bad_entry(bad));
+    }
+    if (e->batch_open) throw BjxError(BJX_ERR_ARG, who + " between bjx_match_batch and its bjx_finish_batch");
+    if (by_nets) {
+      e->qry_net_ips.assign(n_nets, 0);
+      if (net_ips) *net_ips = e->qry_net_ips.data();
+    }
     HIP_OK(hipDeviceSynchronize());
     State &S = e->S;
     hipStream_t st = e->stream;
@@ -1550,8 +1695,11 @@ extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_sta
       F.name = it->second;
     }
     if (bjx_query::empty_window(*f) || !n_ips || !n_st || !n_names) return BJX_OK;
-    if (n_ips >= bjx_snap::kMaxIps) throw BjxError(BJX_ERR_CAPACITY, "bjx_state_query: 2^31 distinct IPs or more");
+    if (n_ips >= bjx_snap::kMaxIps) throw BjxError(BJX_ERR_CAPACITY, who + ": 2^31 distinct IPs or more");
     const bool by_ip = f->ip.ptr != nullptr;
+    std::vector<uint32_t> ip_canon;  // nets and an ip filter: the networks that hold it
+    if (by_nets && by_ip && !T.holds(reinterpret_cast<const uint8_t *>(f->ip.ptr), (uint32_t)f->ip.len, &ip_canon)) return BJX_OK;
+    const bool net_scan = by_nets && !by_ip;
     const uint64_t limit = f->limit;
     const uint64_t room = limit ? (by_ip ? (uint64_t)n_names : n_st) : 0;
     const uint64_t rows_max = std::min(limit, room);
@@ -1572,6 +1720,15 @@ extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_sta
     ExpAlloc tmp;
     uint32_t *keep = by_ip ? nullptr : tmp.get<uint32_t>(n_ips + 1);
     uint32_t *d_sum = tmp.get<uint32_t>(4);
+    // the net table in one image (state_nets.h), sel[], the canonical networks' counters
+    std::vector<uint8_t> net_img;
+    uint64_t o_dir = 0, o_k4 = 0;
+    const uint64_t net_bytes = net_scan ? T.image(&net_img, &o_dir, &o_k4) : 0;
+    const uint32_t n_canon = T.n_canon();
+    uint8_t *d_net = net_scan ? tmp.get<uint8_t>(net_bytes + 16) : nullptr;
+    uint32_t *sel = net_scan ? tmp.get<uint32_t>(n_ips + 1) : nullptr;
+    uint32_t *d_ncnt = net_scan ? tmp.get<uint32_t>((uint64_t)n_canon + 1) : nullptr;
+    unsigned long long *d_found = net_scan ? tmp.get<unsigned long long>(2) : nullptr;
     uint32_t *d_rank = tmp.get<uint32_t>(n_names), *d_by_rank = tmp.get<uint32_t>(n_names);
     uint64_t *d_noff = tmp.get<uint64_t>(n_names + 1);
     uint8_t *d_nbytes = tmp.get<uint8_t>(nbytes.size() + 16);
@@ -1581,7 +1738,8 @@ extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_sta
     uint32_t *i0 = tmp.get<uint32_t>(fin_cap), *i1 = tmp.get<uint32_t>(fin_cap);
     bjx_state_row *d_rows = tmp.get<bjx_state_row>(rows_max);
     uint64_t *d_lens = tmp.get<uint64_t>(rows_max + 1), *d_offs = tmp.get<uint64_t>(rows_max + 1);
-    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_query: no device memory for the candidates");
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, who + ": no device memory for the candidates");
+    if (net_scan) snap_copy_in(e, d_net, net_img.data(), net_bytes);
     HIP_OK(hipMemcpyAsync(d_rank, rank.data(), n_names * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_by_rank, by_rank.data(), n_names * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_noff, noff.data(), (n_names + 1) * 8, hipMemcpyHostToDevice, st));
@@ -1605,11 +1763,29 @@ extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_sta
                          e->q_ip.p, (uint32_t)f->ip.len, F, n_ips, n_names, d_rank, d_ctr, room, cand);
       HIP_OK(hipGetLastError());
     } else {
+      bjx_nets::View V = T.view();
+      if (net_scan) {
+        V.k6 = reinterpret_cast<const uint64_t *>(d_net);
+        V.dir = reinterpret_cast<const bjx_nets::Dir *>(d_net + o_dir);
+        V.k4 = reinterpret_cast<const uint32_t *>(d_net + o_k4);
+        HIP_OK(hipMemsetAsync(d_found, 0, 16, st));
+        HIP_OK(hipMemsetAsync(sel, 0, (n_ips + 1) * 4, st));
+        HIP_OK(hipMemsetAsync(d_ncnt, 0, ((uint64_t)n_canon + 1) * 4, st));
+        hipLaunchKernelGGL(k_net_sel, dim3((unsigned)std::min<uint64_t>(grid_for(n_ips), 8192)), dim3(kBlock), 0, st, n_ips, S.ip_off,
+                           S.ip_len, S.arena, used, V, sel, d_found);
+        HIP_OK(hipGetLastError());
+      }
       HIP_OK(hipMemsetAsync(keep, 0, (n_ips + 1) * 4, st));
       hipLaunchKernelGGL(k_qry_scan, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st, e->st_cap,
-                         S.st, F, n_ips, n_names, d_rank, keep, d_ctr, room, cand);
+                         S.st, F, n_ips, n_names, d_rank, sel, keep, d_ctr, room, cand);
       HIP_OK(hipGetLastError());
       cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceReduce::Sum(t, b, keep, d_sum, (int)n_ips, st); });
+      if (net_scan) {
+        hipLaunchKernelGGL(k_net_count, dim3((unsigned)std::min<uint64_t>((n_ips + kNetCountIps - 1) / kNetCountIps, 2048)), dim3(kBlock),
+                           0, st, n_ips, keep,
+                           S.ip_off, S.ip_len, S.arena, used, V, n_canon, d_ncnt);
+        HIP_OK(hipGetLastError());
+      }
     }
     HIP_OK(hipEventRecord(E.ev[1], st));
     unsigned long long got[2] = {0, 0};
@@ -1618,6 +1794,16 @@ extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_sta
     pin_get(e, &ips_matched, d_sum, 4);
     pin_sync(e);
     ms += E.ms(0, 1);
+    if (net_scan) {
+      std::vector<uint32_t> canon_count(n_canon, 0);
+      if (n_canon) HIP_OK(hipMemcpy(canon_count.data(), d_ncnt, (uint64_t)n_canon * 4, hipMemcpyDeviceToHost));
+      bjx_nets::per_entry(T, canon_count, &e->qry_net_ips);
+    } else if (by_nets && got[0]) {  // an ip filter: that IP is held and has a selected state
+      std::vector<uint32_t> canon_count(n_canon, 0);
+      for (uint32_t c : ip_canon) canon_count[c] = 1;
+      bjx_nets::per_entry(T, canon_count, &e->qry_net_ips);
+    }
+    if (by_nets && net_ips) *net_ips = e->qry_net_ips.data();
     const uint64_t matched = got[0];
     if (matched > n_st || (room && got[1] != matched))
       throw BjxError(BJX_ERR_DEVICE, "internal: query counts disagree with the tables");
@@ -1657,7 +1843,7 @@ extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_sta
         if (!spare) {
           spare = tmp.get<ulonglong2>(in_b);
           spare_cap = in_b;
-          if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_query: no device memory for the selection");
+          if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, who + ": no device memory for the selection");
         }
         nxt = spare;
       } else {
@@ -1705,7 +1891,7 @@ extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_sta
     pin_sync(e);
     ms += E.ms(0, 1);
     uint8_t *d_bytes = tmp.get<uint8_t>(total + 16);
-    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_query: no device memory for the rows' bytes");
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, who + ": no device memory for the rows' bytes");
     HIP_OK(hipEventRecord(E.ev[0], st));
     hipLaunchKernelGGL(k_qry_bytes, dim3(grid_for(n_rows)), dim3(kBlock), 0, st, n_rows, m, fin, i0, S, n_ips, used, d_noff, d_nbytes,
                        d_offs, total, d_rows, d_bytes);
@@ -1724,6 +1910,15 @@ extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_sta
     out->device_ms = ms;
     return BJX_OK;
   });
+}
+
+extern "C" int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_state_rows *out) {
+  return state_query_impl(e, f, nullptr, 0, false, out, nullptr);
+}
+
+extern "C" int bjx_state_query_nets(bjx_engine *e, const bjx_state_filter *f, const bjx_str *nets, size_t n_nets,
+                                    bjx_state_rows *out, const uint64_t **net_ips) {
+  return state_query_impl(e, f, nets, n_nets, true, out, net_ips);
 }
 
 extern "C" size_t bjx_state_dump(bjx_engine *e, char *out, size_t cap) {

@@ -400,45 +400,69 @@ class Engine:
     _query = "bjx_state_query"
 
     def state_query(self, ip=None, name=None, min_hits: int = INT64_MIN, min_start_ns: int = INT64_MIN,
-                    max_start_ns: int = INT64_MAX, order: int = _lib.QUERY_BY_HITS, limit: int = 100) -> dict:
+                    max_start_ns: int = INT64_MAX, order: int = _lib.QUERY_BY_HITS, limit: int = 100, nets=None) -> dict:
         """Counts and the first `limit` states that pass the filter
         (bjx_state_query; banjax_amd/state_query.py documents the order and is
         its model).  ip / name None: every IP / rule name; b"" is a value.
         order: _lib.QUERY_BY_HITS or _lib.QUERY_BY_START (or "hits" / "start").
         limit 0: the counts only.  Returns {"n_matched", "n_ips_matched",
         "rows": [(ip, name, hits, start_ns)] (bytes, bytes, int, int),
-        "device_ms"}.  The engine is unchanged."""
+        "device_ms"}.  The engine is unchanged.
+        nets (an iterable of "IP" / "IP/len" entries, str or bytes; not None):
+        only states whose IP lies in one of these networks
+        (bjx_state_query_nets; banjax_amd/state_nets.py is the model of the
+        entries and of membership).  The answer gains "net_ips": per entry, in
+        the order given, the distinct IPs inside it with a selected state."""
         order = {"hits": _lib.QUERY_BY_HITS, "start": _lib.QUERY_BY_START}.get(order, order)
         ipb = None if ip is None else _lib.b(ip)
         nb = None if name is None else _lib.b(name)
         f = _lib.StateFilter(_lib.Str(ipb, len(ipb or b"")), _lib.Str(nb, len(nb or b"")), min_hits, min_start_ns,
                              max_start_ns, order, limit)
         out = _lib.StateRows()
-        self._check(getattr(_lib.lib(), self._query)(self._h, C.byref(f), C.byref(out)), "state_query")
+        if nets is None:
+            self._check(getattr(_lib.lib(), self._query)(self._h, C.byref(f), C.byref(out)), "state_query")
+        else:
+            lst = [_lib.b(x) for x in nets]
+            arr = (_lib.Str * max(len(lst), 1))(*[_lib.Str(x, len(x)) for x in lst])
+            counts = C.POINTER(C.c_uint64)()
+            self._check(getattr(_lib.lib(), self._query + "_nets")(self._h, C.byref(f), arr, len(lst), C.byref(out),
+                                                                   C.byref(counts)), "state_query")
         blob = C.string_at(out.bytes, out.n_bytes) if out.n_bytes else b""
         rows = []
         for k in range(out.n_rows):
             r = out.rows[k]
             rows.append((blob[r.ip_off:r.ip_off + r.ip_len], blob[r.name_off:r.name_off + r.name_len], r.hits, r.start_ns))
-        return {"n_matched": out.n_matched, "n_ips_matched": out.n_ips_matched, "rows": rows, "device_ms": out.device_ms}
+        ans = {"n_matched": out.n_matched, "n_ips_matched": out.n_ips_matched, "rows": rows, "device_ms": out.device_ms}
+        if nets is not None:
+            ans["net_ips"] = [counts[k] for k in range(len(lst))]
+        return ans
 
     _remove = "bjx_state_remove"
 
     def state_remove(self, ips=None, ip=None, name=None, min_hits: int = INT64_MIN, min_start_ns: int = INT64_MIN,
-                     max_start_ns: int = INT64_MAX) -> dict:
+                     max_start_ns: int = INT64_MAX, nets=None) -> dict:
         """Forget every state that passes the filter (state_query's ip, name,
         min_hits, min_start_ns, max_start_ns) and, with `ips` (an iterable of
         str / bytes; None or empty: no list, as n_ips == 0 in C), whose IP is listed; every IP left without
         a state goes too (bjx_state_remove; banjax_amd/state_remove.py is its
         model).  Nothing selected: the engine is left exactly as it was.
-        Returns the bjx_remove_stats fields."""
+        nets (an iterable of "IP" / "IP/len" entries; not None, and then
+        without `ips`): the states whose IP lies in one of these networks
+        (bjx_state_remove_nets); an empty or malformed nets is an error, never
+        "every IP".  Returns the bjx_remove_stats fields."""
+        if nets is not None and ips is not None:
+            raise ValueError("state_remove: ips and nets together")
         ipb = None if ip is None else _lib.b(ip)
         nb = None if name is None else _lib.b(name)
         f = _lib.StateFilter(_lib.Str(ipb, len(ipb or b"")), _lib.Str(nb, len(nb or b"")), min_hits, min_start_ns,
                              max_start_ns, _lib.QUERY_BY_HITS, 0)
-        lst = [] if ips is None else [_lib.b(x) for x in ips]
+        lst = [_lib.b(x) for x in (nets if nets is not None else ips or [])]
         arr = (_lib.Str * max(len(lst), 1))(*[_lib.Str(x, len(x)) for x in lst])
         st = _lib.RemoveStats()
+        if nets is not None:
+            self._check(getattr(_lib.lib(), self._remove + "_nets")(self._h, C.byref(f), arr, len(lst), C.byref(st)),
+                        "state_remove")
+            return {k: getattr(st, k) for k, _ in _lib.RemoveStats._fields_}
         self._check(getattr(_lib.lib(), self._remove)(self._h, C.byref(f), arr if lst else None, len(lst), C.byref(st)),
                     "state_remove")
         return {k: getattr(st, k) for k, _ in _lib.RemoveStats._fields_}

@@ -452,15 +452,18 @@ class RegexRateLimitStates:
         return out if out else None
 
     def remove(self, ips=None, ip=None, name=None, min_hits: int = _INT64_MIN, min_start_ns: int = _INT64_MIN,
-               max_start_ns: int = _INT64_MAX) -> dict:
+               max_start_ns: int = _INT64_MAX, nets=None) -> dict:
         """Forget chosen states, which the reference's host does with delete on
         its map (Engine.state_remove): those that pass the filter and, with
         `ips`, whose IP is listed; an IP left without a state goes too.
         remove(ips=[ip]) after an unban gives the IP a fresh start,
         remove(name=rule) after a reload forgets what was counted under the
-        rule's old rate.  Returns the bjx_remove_stats fields."""
+        rule's old rate.  remove(nets=["10.8.0.0/16"]) does it for every
+        address of a network ("IP" or "IP/len" entries, as a global Allow
+        list writes them; Engine.state_remove's nets) -- a new allow entry, an
+        unbanned range.  Returns the bjx_remove_stats fields."""
         return self._e.state_remove(ips=ips, ip=ip, name=name, min_hits=min_hits, min_start_ns=min_start_ns,
-                                    max_start_ns=max_start_ns)
+                                    max_start_ns=max_start_ns, nets=nets)
 
     def __len__(self):
         return self._e.state_len()

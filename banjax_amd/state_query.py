@@ -19,6 +19,11 @@ which is total -- (IP, name) is unique -- and depends on the logical state
 alone: not on slot layout, table sizes, the ids names were interned under or
 the debug hash mask.  The answer is the number of passing states, the number
 of distinct IPs among them and the first min(limit, n_matched) of them.
+
+With nets (bjx_state_query_nets; entries and membership: state_nets.py) a state
+passes only when its IP lies in one of the networks, and the answer gains
+net_ips: per entry, in the order given, the distinct IPs inside it that have a
+passing state.
 """
 from __future__ import annotations
 
@@ -32,11 +37,14 @@ def _b(x) -> bytes:
 
 
 def select(ips_in_order, states, ip=None, name=None, min_hits=INT64_MIN, min_start_ns=INT64_MIN,
-           max_start_ns=INT64_MAX, order=BY_HITS, limit=0):
+           max_start_ns=INT64_MAX, order=BY_HITS, limit=0, nets=None):
     """ips_in_order, states: what snapshot.parse returns (or the arguments of
     snapshot.build): the IPs in first-seen order and {ip: {rule name: (hits,
     start_ns)}}.  -> (n_matched, n_ips_matched, [(ip, name, hits, start_ns)])
-    with ip and name as bytes."""
+    with ip and name as bytes; with nets (not None: a list of entries) a
+    fourth element, net_ips."""
+    from .state_nets import Nets
+    table = None if nets is None else Nets(nets)
     if order not in (BY_HITS, BY_START):
         raise ValueError("order")
     if not 0 <= limit <= MAX_ROWS:
@@ -51,6 +59,8 @@ def select(ips_in_order, states, ip=None, name=None, min_hits=INT64_MIN, min_sta
         seen.add(i)
         if want_ip is not None and i != want_ip:
             continue
+        if table is not None and not table.holds(i):
+            continue
         for n, (hits, start) in states.get(i, {}).items():
             if want_name is not None and n != want_name:
                 continue
@@ -58,4 +68,10 @@ def select(ips_in_order, states, ip=None, name=None, min_hits=INT64_MIN, min_sta
                 passing.append((-(start if order == BY_START else hits), pos, n, i, hits, start))
     passing.sort(key=lambda t: t[:3])
     rows = [(i, n, hits, start) for _, _, n, i, hits, start in passing[:limit]]
-    return len(passing), len({t[1] for t in passing}), rows
+    if table is None:
+        return len(passing), len({t[1] for t in passing}), rows
+    net_ips = [0] * len(table.entries)
+    for i in {t[3] for t in passing}:
+        for k in table.which(i):
+            net_ips[k] += 1
+    return len(passing), len({t[1] for t in passing}), rows, net_ips

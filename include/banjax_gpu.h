@@ -430,7 +430,8 @@ int bjx_state_query(bjx_engine *e, const bjx_state_filter *f, bjx_state_rows *ou
    unban (the reference's POST /unban, http_server.go:262-312, clears the
    decision and leaves the IP's counters, often exactly at their threshold),
    a rule whose rate or regex changed on reload (state is keyed by rule name
-   and survives it), a new allow-list entry, a false positive found with
+   and survives it), a new allow-list entry (a single IP; for an IP/len entry
+   use bjx_state_remove_nets below), a false positive found with
    bjx_state_query.
 
    Selection: a state is dropped when it has valid != 0 and passes the five
@@ -479,6 +480,54 @@ typedef struct bjx_remove_stats {   /* 80 B */
   double device_ms;                          /* HIP events, copies excluded */
 } bjx_remove_stats;
 int bjx_state_remove(bjx_engine *e, const bjx_state_filter *f, const bjx_str *ips, size_t n_ips, bjx_remove_stats *out);
+/* ---- Nets: bjx_state_query and bjx_state_remove with the IPs chosen by
+   network.  Uses: a new allow-list entry IP/len (the counters of every address
+   in it stay in HBM otherwise), unbanning a range, "what is this /24 doing".
+
+   Entries: nets[k] is text as an Allow entry of a decision list is written,
+   an address or address/bits, read by net.ParseIP / net.ParseCIDR rules (no
+   zone; bits in decimal, at most the family's length; bits equal to it is the
+   single address; host bits set in the address are masked away).
+   BJX_ERR_ARG, with the engine unchanged: an entry that does not parse (the
+   message names its index), n_nets == 0 (a nets call never means "every IP"),
+   n_nets > BJX_NETS_MAX, NULL nets, an entry with len > 0 and a NULL ptr, and
+   what bjx_state_query / bjx_state_remove refuse in *f.
+
+   Membership: a held IP is in a network exactly when a global Allow decision
+   list made of these entries would exempt a line of that IP
+   (CheckIsAllowed).  The IP's stored bytes are parsed as net.ParseIP parses
+   them; text that does not parse is in no network.  A v4-mapped address
+   compares as IPv4, against IPv4 networks only, and an IPv6 network never
+   holds it: ::/0 holds no IPv4 text, 0.0.0.0/0 no IPv6 text, and
+   ::ffff:10.0.0.0/104 is 10.0.0.0/8.  Duplicate and nested entries are fine.
+
+   Selection: a state is selected when it has valid != 0, passes the five
+   conditions of *f exactly as bjx_state_query reads them and its IP is in at
+   least one entry.  f->ip together with nets means both: that IP, and only
+   when a network holds it.
+
+   bjx_state_query_nets: order, limit, rows, bytes, ownership, locking and the
+   open-batch rule are bjx_state_query's; n_matched and n_ips_matched count the
+   selected states and their distinct IPs.  (*net_ips)[k], for each of the
+   n_nets entries in the caller's order, is the number of distinct held IPs
+   inside entry k with at least one selected state; nested and duplicate
+   entries each count, so the sum may exceed n_ips_matched.  net_ips may be
+   NULL; the array is engine-owned and valid until the next query on the
+   handle.  A counts-only call (limit 0) previews bjx_state_remove_nets with
+   the same arguments: its n_matched is the removal's states_dropped.
+
+   bjx_state_remove_nets: everything bjx_state_remove promises, with "the IP
+   is in a network" in place of "the IP is in the list": the result equals an
+   engine that imported a snapshot of the survivors, first-seen order kept, ids
+   dense; nothing selected leaves the engine exactly as it was; the new tables
+   are allocated before the old ones are freed.  ips_found is the number of
+   distinct held IPs inside any network, whether or not a state of theirs was
+   selected.  out may be NULL. */
+#define BJX_NETS_MAX 65536
+int bjx_state_query_nets(bjx_engine *e, const bjx_state_filter *f, const bjx_str *nets, size_t n_nets,
+                         bjx_state_rows *out, const uint64_t **net_ips);
+int bjx_state_remove_nets(bjx_engine *e, const bjx_state_filter *f, const bjx_str *nets, size_t n_nets,
+                          bjx_remove_stats *out);
 /* RegexRateLimitStates.String(): "ip:\n\trule:\n\t\t{hits start}\n" blocks, IPs in
    first-seen order.  Returns the full length (writes at most cap bytes). */
 size_t bjx_state_dump(bjx_engine *e, char *out, size_t cap);
@@ -705,6 +754,17 @@ int bjx_node_state_query(bjx_node *n, const bjx_state_filter *f, bjx_state_rows 
    is idempotent, so the caller repeats the call (the repeat's stats count
    what it still found).  out may be NULL. */
 int bjx_node_state_remove(bjx_node *n, const bjx_state_filter *f, const bjx_str *ips, size_t n_ips, bjx_remove_stats *out);
+/* bjx_state_query_nets / bjx_state_remove_nets over the node.  Every engine
+   gets the same filter and nets (with an ip filter too).  Rows are merged as
+   bjx_node_state_query merges them; net_ips and the removal's stats are
+   summed, exactly, because an IP lives on one engine; device_ms is the slowest
+   shard's.  net_ips is node-owned until the next query on the node.  Both wait
+   for the node batch, as bjx_node_state_expire does.  On removal every shard
+   is asked and the first failure is returned, as in bjx_node_state_remove. */
+int bjx_node_state_query_nets(bjx_node *n, const bjx_state_filter *f, const bjx_str *nets, size_t n_nets,
+                              bjx_state_rows *out, const uint64_t **net_ips);
+int bjx_node_state_remove_nets(bjx_node *n, const bjx_state_filter *f, const bjx_str *nets, size_t n_nets,
+                               bjx_remove_stats *out);
 /* bjx_batch_rule_stats / bjx_rule_stats_total / bjx_rule_stats_reset over the
    node: the engines' arrays summed (engine k counted chunk k's lines),
    n_lines summed, device_ms the slowest engine's (totals: those summed). */
