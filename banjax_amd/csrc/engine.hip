@@ -5306,8 +5306,9 @@ static void calibrate_grams(const std::vector<uint8_t> &lit_bytes, const std::ve
                             std::vector<uint32_t> &lit_gram, std::vector<uint8_t> &lit_chk, const uint8_t *sample,
                             size_t n) {
   lit_chk.assign(lit_off.size(), 0);
+  // (an anchor literal may be shorter than 4 bytes: it has no window, and its check is its first word)
   for (size_t id = 0; id < lit_off.size(); ++id)
-    lit_chk[id] = (uint8_t)(lit_gram[id] >= (lit_len[id] - 4) / 2 ? 0 : lit_len[id] - 4);
+    if (lit_len[id] >= 4) lit_chk[id] = (uint8_t)(lit_gram[id] >= (lit_len[id] - 4) / 2 ? 0 : lit_len[id] - 4);
   if (n < 4 || lit_off.empty()) return;
   std::unordered_map<uint32_t, uint32_t> cnt;
   std::vector<uint64_t> seen(1u << 14, 0);  // 2^20-bit presence filter
@@ -5361,6 +5362,7 @@ static void calibrate_grams(const std::vector<uint8_t> &lit_bytes, const std::ve
   }
   std::unordered_map<uint32_t, uint32_t> load;  // gram -> literals filed under it
   auto file = [&](size_t id, int d) {
+    if (lit_len[id] < 4) return;  // no window to file
     uint32_t vs[16];
     const uint32_t k = variants(id, lit_gram[id], vs);
     for (uint32_t i = 0; i < k; ++i) load[vs[i]] += d;
@@ -6397,6 +6399,12 @@ void bind_ruleset(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *sample, s
     for (uint32_t k = 0; k < lit_len[i]; ++k) {
       lb_al.push_back(lit_bytes[lit_off[i] + k]);
       cm_al.push_back(lit_ci[lit_off[i] + k] ? 0x20 : 0);
+    }
+    // literal_at compares a whole word first: in a literal shorter than that (an anchor
+    // literal of 1-3 bytes) the rest of the word matches any text, mask and bytes all ones
+    for (uint32_t k = lit_len[i]; k < 4; ++k) {
+      lb_al.push_back(0xFF);
+      cm_al.push_back(0xFF);
     }
     const size_t padded = ((lb_al.size() + 3) & ~size_t(3)) + 4;
     lb_al.resize(padded, 0);

@@ -9,6 +9,7 @@ import pytest
 from banjax_amd import Config, Ruleset, _lib
 from oracle import oracle as O
 from tests import long_lines as LL
+from tests import rule_corpus as RC
 from tests.parity import oracle_config
 
 SEEDS = (1, 2)  # the seeds tests/test_gpu_long_line_hits.py feeds
@@ -17,16 +18,8 @@ TILE, HALO = LL.TILE, LL.HALO
 
 def _rule_literals(rs, i):
     """(mode, [(bytes, ci)]) of rule i from bjx_debug_rule_literal."""
-    L = _lib.lib()
-    n = L.bjx_debug_rule_literal(rs.handle, i, None, 0)
-    buf = bytes(n)
-    L.bjx_debug_rule_literal(rs.handle, i, buf, n)
-    rows = buf.split(b"\n")
-    lits = []
-    for row in rows[1:]:
-        _, ci, s = row.split(b" ", 2)
-        lits.append((s, b"1" in ci))
-    return int(rows[0].split()[0]), lits
+    plan = RC.read_plan(_lib.lib(), rs.handle, i)
+    return plan.mode, [(l.s, l.any_ci) for l in plan.literals]
 
 
 @pytest.mark.parametrize("kind", LL.RULESETS)

@@ -9,6 +9,7 @@ import pytest
 from banjax_amd import Config, Ruleset, _lib
 from oracle import oracle as O
 from tests import long_lines as LL
+from tests import rule_corpus as RC
 from tests import wide_scopes as WS
 from tests.parity import oracle_config
 
@@ -26,19 +27,16 @@ def test_rulesets_compile_as_meant(kind):
     L = _lib.lib()
     n_pref = 0
     for i, r in enumerate(want):
-        n = L.bjx_debug_rule_literal(rs.handle, i, None, 0)
-        buf = bytes(n)
-        L.bjx_debug_rule_literal(rs.handle, i, buf, n)
-        rows = buf.split(b"\n")
-        mode, equiv = (int(x) for x in rows[0].split())
+        buf = RC.read_plan(L, rs.handle, i)
+        mode, equiv = buf.mode, buf.equiv
         assert mode == r.mode, (r.name, r.regex, buf)
-        lits = [(row.split(b" ", 2)[2], b"1" in row.split(b" ", 2)[1]) for row in rows[1:]]
+        lits = [(l.s, l.any_ci) for l in buf.literals]
         assert lits == r.lits, (r.name, r.regex, buf)
         if mode == WS.MODE_PREFILTER:
             n_pref += 1
             assert bool(equiv) == r.equiv, (r.name, buf)
         if mode == WS.MODE_ANCHORED and r.lits:
-            assert rows[1].startswith(b"^=" if r.equiv else b"^~"), (r.name, buf)
+            assert buf.anchor and buf.anchor_equiv == r.equiv, (r.name, buf)  # ^= rows or ^~ rows
         if r.letter == "i":  # the literal spells the rule's own host; the scan looks for the host-free piece
             assert r.site.encode() in lits[0][0] and WS.piece_of(lits[0][0], r.site) in (b" POST /xmlrpc.php", b" GET /wp-login.php HTTP/",
                                                                                         b" POST /xmlrpcB.php", b" GET /wp-loginB.php HTTP/")
