@@ -356,6 +356,8 @@ def lib():
     L.bjx_debug_set_rule_stats_lds.argtypes = [vp, C.c_uint32]
     L.bjx_debug_rule_stats_path.restype = C.c_int
     L.bjx_debug_rule_stats_path.argtypes = [vp]
+    L.bjx_debug_job_counts.restype = C.c_int
+    L.bjx_debug_job_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, C.POINTER(C.c_uint32)]
     _lib = L
     return L
 

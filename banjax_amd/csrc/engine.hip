@@ -5144,6 +5144,7 @@ struct bjx_engine {
   DevBuf<uint32_t> jline, jkey, jidx, jidx2, jkey2;  // jobs by slot (line, key, slot), the sorted keys and slots
   DevBuf<uint64_t> jrec;                           // job window records by slot (kJob*)
   uint64_t last_jobs = 0, last_long_runs = 0;
+  uint32_t last_job_rules = 0, last_line_passes = 0;  // bjx_debug_job_counts: the batch's n_rules, runs of its per-line pass
   DevBuf<uint64_t> long_heads;
   DevBuf<uint64_t> lr_end, lr_len, lr_off, lr_win;
   DevBuf<unsigned long long> chk;
@@ -7390,6 +7391,7 @@ static bool match_phase(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *byt
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((work + kBlock - 1) / kBlock, resident));
   };
   for (int attempt = 0;; ++attempt) {
+    e->last_line_passes = (uint32_t)attempt + 1;
     LinesArgs A;
     A.buf = buf; A.n = n; A.nl = e->nl.p; A.n_lines = n_lines; A.L = L; A.now_ns = now_ns;
     A.dbg = getenv("BJX_DEBUG_LINES") ? (uint32_t)atoi(getenv("BJX_DEBUG_LINES")) : 0u;
@@ -7518,6 +7520,7 @@ static bool match_phase(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *byt
   // job slots taken (sc4[3]; the chunks' unused ones hold null jobs) and real jobs (n_jobs)
   const unsigned long long n_slow = sc4[4], n_slots = sc4[3];
   e->last_jobs = n_jobs;
+  e->last_job_rules = B.n_rules;
   e->scan_stats[0] = sc4[0]; e->scan_stats[1] = sc4[1]; e->scan_stats[2] = n_slow; e->scan_stats[3] = B.scan_img_bytes;
   e->scan_stats[4] = n_jobs; e->scan_stats[5] = sc4[2];
   HIP_OK(hipEventRecord(e->evk[2], st));
@@ -7525,7 +7528,7 @@ static bool match_phase(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *byt
     // group the jobs by rule (stable: line order inside a rule), then one lane per job
     e->jidx2.ensure(n_slots); e->jkey2.ensure(n_slots);
     {
-      // null jobs (key n_rules) sort after the real ones: k_dfa takes the first n_jobs
+      // null jobs (key 2 * n_rules) sort after the real ones: k_dfa takes the first n_jobs
       uint32_t *ki = e->jkey.p, *ko = e->jkey2.p, *vi = e->jidx.p, *vo = e->jidx2.p;
       const int bits = std::max(1, bit_width(2 * B.n_rules));
       cub_call(e, [&](void *tmp, size_t &bytes) {
@@ -8465,6 +8468,37 @@ extern "C" int bjx_debug_state_slots(bjx_engine *e, const uint8_t *ip_bytes, con
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(slots, d_out, n * 8, hipMemcpyDeviceToHost, e->stream));
     HIP_OK(hipStreamSynchronize(e->stream));
+    return BJX_OK;
+  });
+}
+extern "C" int bjx_debug_job_counts(bjx_engine *e, uint32_t *windowed, uint32_t *legacy, size_t n_rules,
+                                    uint32_t *line_pass_runs) {
+  if (!e || (n_rules && (!windowed || !legacy))) return BJX_ERR_ARG;
+  return guarded(e, [&]() -> int {
+    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_debug_job_counts between bjx_match_batch and its bjx_finish_batch");
+    if (n_rules != e->last_job_rules) throw BjxError(BJX_ERR_ARG, "bjx_debug_job_counts: n_rules is not the last batch's");
+    if (line_pass_runs) *line_pass_runs = e->last_line_passes;
+    for (size_t r = 0; r < n_rules; ++r) windowed[r] = legacy[r] = 0;
+    const uint64_t n_jobs = e->last_jobs;
+    if (!n_jobs || !n_rules) return BJX_OK;
+    // the batch's sorted keys are still in jkey2 (a batch without jobs leaves an
+    // older batch's there: last_jobs is 0 then); ranges as run_nfa_jobs takes them
+    hipStream_t st = e->stream;
+    HIP_OK(hipSetDevice(e->device));
+    const uint32_t nk = 2 * (uint32_t)n_rules;
+    e->rb_first.ensure(nk); e->rb_last.ensure(nk);
+    HIP_OK(hipMemsetAsync(e->rb_first.p, 0, nk * 4ull, st));
+    HIP_OK(hipMemsetAsync(e->rb_last.p, 0, nk * 4ull, st));
+    hipLaunchKernelGGL(k_rule_bounds, dim3(grid_for(n_jobs)), dim3(kBlock), 0, st, n_jobs, e->jkey2.p, e->rb_first.p, e->rb_last.p);
+    HIP_OK(hipGetLastError());
+    std::vector<uint32_t> f(nk), l(nk);
+    HIP_OK(hipMemcpyAsync(f.data(), e->rb_first.p, nk * 4ull, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(l.data(), e->rb_last.p, nk * 4ull, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (size_t r = 0; r < n_rules; ++r) {
+      windowed[r] = l[r] > f[r] ? l[r] - f[r] : 0u;
+      legacy[r] = l[n_rules + r] > f[n_rules + r] ? l[n_rules + r] - f[n_rules + r] : 0u;
+    }
     return BJX_OK;
   });
 }

@@ -190,6 +190,7 @@ class Engine:
             rc = _lib.lib().bjx_process_batch(self._h, rs.handle, C.c_char_p(buf), len(buf), now_ns, flags,
                                               C.byref(res))
         self._check(rc, "process_batch")
+        self._batch_rules = len(rs)
         return BatchOutput(res, copy_results)
 
     # ---- multi-GPU batch (include/banjax_gpu.h); buffers are device pointers
@@ -199,6 +200,7 @@ class Engine:
         flags = (_lib.COPY_RESULTS if copy_results else 0) | _lib.INPUT_DEVICE
         self._check(_lib.lib().bjx_match_batch(self._h, rs.handle, C.c_void_p(device_ptr), nbytes, now_ns, flags,
                                                C.byref(res)), "match_batch")
+        self._batch_rules = len(rs)
         return res
 
     def events_partition(self, n_parts: int) -> List[Tuple[int, int, int]]:
@@ -344,6 +346,17 @@ class Engine:
         self._check(_lib.lib().bjx_debug_state_slots(self._h, blob.ctypes.data, off.ctypes.data, arr, len(table),
                                                      idx.ctypes.data, n, out.ctypes.data), "debug_state_slots")
         return out
+
+    def debug_job_counts(self):
+        """Test hook: the last batch's sorted DFA jobs per rule of its ruleset,
+        (windowed, legacy, line_pass_runs): the counts under the job keys r and
+        n_rules + r, and how often the per-line pass ran (2 when the job buffers
+        grew).  Computed on demand (bjx_debug_job_counts)."""
+        n = getattr(self, "_batch_rules", 0)
+        w, l = (C.c_uint32 * max(1, n))(), (C.c_uint32 * max(1, n))()
+        runs = C.c_uint32()
+        self._check(_lib.lib().bjx_debug_job_counts(self._h, w, l, n, C.byref(runs)), "debug_job_counts")
+        return list(w[:n]), list(l[:n]), runs.value
 
     def state_clear(self):
         self._check(_lib.lib().bjx_state_clear(self._h), "state_clear")

@@ -95,6 +95,16 @@ int bjx_debug_set_rule_stats_lds(bjx_engine *e, uint32_t max_rules);
 /* where the engine's last BJX_RULE_STATS batch binned: 1 LDS, 2 the global
    counters, 0 nothing was launched (no results) */
 int bjx_debug_rule_stats_path(bjx_engine *e);
+/* Test hook: what the DFA job stage of the engine's last batch (the last one
+   that held a complete line) saw.  For each of the n_rules rules of that
+   batch's ruleset (any other n_rules is BJX_ERR_ARG): its sorted jobs under the windowed key r (k_dfa's) and under
+   the legacy key n_rules + r (k_dfa_legacy's, k_nfa's, k_nfa_wide's); their
+   sum over the rules is bjx_debug_scan_stats' DFA jobs.  line_pass_runs (may be
+   null): how often the per-line pass ran, 1, or 2 when the job buffers grew.
+   Computed on demand from the sorted keys the batch left on the device (one
+   k_rule_bounds launch); a batch that does not call it runs the same kernels
+   with the same arguments as without the hook. */
+int bjx_debug_job_counts(bjx_engine *e, uint32_t *windowed, uint32_t *legacy, size_t n_rules, uint32_t *line_pass_runs);
 #ifdef __cplusplus
 }
 #endif
