@@ -113,6 +113,7 @@ EXPORTS = [
     "bjx_state_query", "bjx_node_state_query",
     "bjx_state_remove", "bjx_node_state_remove",
     "bjx_state_query_nets", "bjx_node_state_query_nets", "bjx_state_remove_nets", "bjx_node_state_remove_nets",
+    "bjx_state_trim", "bjx_node_state_trim",
     "bjx_batch_rule_stats", "bjx_rule_stats_total", "bjx_rule_stats_reset",
     "bjx_node_batch_rule_stats", "bjx_node_rule_stats_total", "bjx_node_rule_stats_reset",
 ]
@@ -164,6 +165,25 @@ class RemoveStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("states_before", "states_dropped", "ips_before", "ips_dropped", "ips_found",
                                             "arena_bytes_before", "arena_bytes_after", "device_bytes_before",
                                             "device_bytes_after")] + [("device_ms", C.c_double)]
+
+
+TRIM_DRY_RUN = 1
+TRIM_BY_NONE, TRIM_BY_FLOOR, TRIM_BY_STATES, TRIM_BY_IPS = 0, 1, 2, 3
+
+
+class TrimBudget(C.Structure):
+    """bjx_trim_budget: how much state a bjx_state_trim may leave (32 B)."""
+    _fields_ = [("max_states", C.c_uint64), ("max_ips", C.c_uint64), ("floor_cutoff_ns", C.c_int64),
+                ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class TrimStats(C.Structure):
+    """bjx_trim_stats: the cutoff one bjx_state_trim found, what it dropped and freed (104 B)."""
+    _fields_ = [("cutoff_ns", C.c_int64), ("bound", C.c_uint32), ("budget_met", C.c_uint32)] + \
+               [(k, C.c_uint64) for k in ("states_before", "states_dropped", "states_dropped_live", "ips_before",
+                                          "ips_dropped", "arena_bytes_before", "arena_bytes_after",
+                                          "device_bytes_before", "device_bytes_after")] + \
+               [("select_ms", C.c_double), ("device_ms", C.c_double)]
 
 
 class RuleStat(C.Structure):
@@ -346,6 +366,11 @@ def lib():
     for name in ("bjx_state_remove_nets", "bjx_node_state_remove_nets"):
         f = getattr(L, name)
         f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(Str), sz, C.POINTER(RemoveStats)]
+    for name in ("bjx_state_trim", "bjx_node_state_trim"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = C.c_int, [vp, C.POINTER(TrimBudget), C.POINTER(TrimStats)]
+    L.bjx_debug_set_trim_grid.restype = C.c_int
+    L.bjx_debug_set_trim_grid.argtypes = [vp, C.c_uint32]
     for pre in ("bjx_", "bjx_node_"):
         for name in ("batch_rule_stats", "rule_stats_total"):
             f = getattr(L, pre + name)

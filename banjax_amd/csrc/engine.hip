@@ -48,6 +48,7 @@
 #include "state_query.h"
 #include "state_remove.h"
 #include "state_nets.h"
+#include "state_trim.h"
 
 using namespace bjx;
 
@@ -5119,6 +5120,7 @@ struct bjx_engine {
   uint32_t lines2_w = 0;       // ... and the instance (mask width) it was set on
   int dbg_slot_cache = -1;     // bjx_debug_set_slot_cache: -1 = BJX_SLOT_CACHE / default on, 0 off, 1 on
   uint32_t dbg_bucket_bits = 0;  // bjx_debug_set_bucket_bits: 0 = kBucketBits, else the grouping's high slot bits
+  uint32_t dbg_trim_grid = 0;    // bjx_debug_set_trim_grid: 0 = default, else the block cap of the trim's counting passes
   uint64_t host_counters[3] = {0, 0, 0};
   // host_counters were read with the match phase's last counts, nothing has
   // touched the tables since (run_batch: match, then straight to the rate limit)
@@ -8427,6 +8429,12 @@ extern "C" int bjx_debug_set_bucket_bits(bjx_engine *e, uint32_t bits) {
   if (!e || bits > (uint32_t)kBucketBits) return BJX_ERR_ARG;
   std::lock_guard<std::mutex> g(e->mu);
   e->dbg_bucket_bits = bits;
+  return BJX_OK;
+}
+extern "C" int bjx_debug_set_trim_grid(bjx_engine *e, uint32_t max_blocks) {
+  if (!e) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->dbg_trim_grid = max_blocks;
   return BJX_OK;
 }
 extern "C" int bjx_debug_state_slots(bjx_engine *e, const uint8_t *ip_bytes, const uint32_t *ip_off, const bjx_str *names,

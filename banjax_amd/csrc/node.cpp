@@ -46,6 +46,7 @@
 #include "snapshot.h"
 #include "state_query.h"
 #include "state_remove.h"
+#include "state_trim.h"
 #include "state_nets.h"
 
 namespace {
@@ -1139,6 +1140,42 @@ extern "C" int bjx_node_state_remove_nets(bjx_node *n, const bjx_state_filter *f
       bjx_remove::add(&t, s);
     }
     if (first_rc != BJX_OK) fail(first_rc, first_msg);
+    if (out) *out = t;
+    return BJX_OK;
+  });
+}
+
+// the selection on every engine, the largest cutoff applied on every engine
+// (state_trim.h: node_pick, add).  A failed selection stops before anything is
+// applied; when applying, every engine is asked and the first failure returned
+extern "C" int bjx_node_state_trim(bjx_node *n, const bjx_trim_budget *b, bjx_trim_stats *out) {
+  if (!n) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    if (const char *why = bjx_trim::check_budget(b)) fail(BJX_ERR_ARG, std::string("bjx_node_state_trim: ") + why);
+    const size_t N = n->parts.size();
+    std::vector<bjx_trim::Picked> picked(N);
+    int first_rc = BJX_OK;
+    std::string first_msg;
+    auto note = [&](int rc, size_t k) {
+      if (rc == BJX_OK || first_rc != BJX_OK) return;
+      first_rc = rc;
+      first_msg = "engine " + std::to_string(k) + ": " + bjx_engine_last_error(n->parts[k].e);
+    };
+    for (size_t k = 0; k < N; ++k) note(bjx_trim_select(n->parts[k].e, b, &picked[k]), k);
+    if (first_rc != BJX_OK) fail(first_rc, first_msg);
+    const bjx_trim::Picked P = bjx_trim::node_pick(picked.data(), N);
+    bjx_trim_stats t{};
+    for (size_t k = 0; k < N; ++k) {
+      bjx_trim_stats s{};
+      const int rc = bjx_trim_apply(n->parts[k].e, P.cutoff, b->floor_cutoff_ns, b->flags, &s);
+      note(rc, k);
+      if (rc != BJX_OK) continue;
+      s.select_ms = picked[k].select_ms;
+      s.device_ms += picked[k].select_ms;
+      bjx_trim::add(&t, s);
+    }
+    if (first_rc != BJX_OK) fail(first_rc, first_msg);
+    t.cutoff_ns = P.cutoff; t.bound = P.bound; t.budget_met = P.budget_met;
     if (out) *out = t;
     return BJX_OK;
   });

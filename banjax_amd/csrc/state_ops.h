@@ -1959,3 +1959,266 @@ extern "C" size_t bjx_state_dump(bjx_engine *e, char *out, size_t cap) {
   });
   return size;
 }
+
+// ---- trim: bjx_state_trim (the budget's checks, the select's host step, the
+// cutoff from the candidates, the node's max and sum: state_trim.h).  The
+// cutoff is a k-th largest over interval_start_ns -- of all states, and of the
+// newest start per IP -- found by an MSB-first radix select that moves no
+// state: each pass counts, by the next digit, the keys that carry the digits
+// fixed so far, reading the 32-byte slots in place; the host picks the digit
+// the rank falls into (bjx_trim::step).  The key is the start with its sign bit
+// flipped (unsigned order = signed order), five digits of 13, 13, 13, 13, 12 bits.
+// The first pass over the table also takes each IP's newest start (a 64-bit
+// atomicMax into newest[ip id]) and marks the IPs that hold a state (one bit
+// each); the select over the IPs then reads that array.  Starts cluster in
+// time, so almost every key has the same high digits: a thread counts a run of
+// equal digits before it touches LDS, as k_qry_hist does.  The mark pass that
+// follows is k_exp_mark with two more counters, the rebuild the expiry's own.
+namespace {
+
+__device__ __forceinline__ void trim_count(uint32_t *s_h, uint32_t d, uint32_t &run_d, uint32_t &run_n) {
+  if (d != run_d && run_n) {
+    atomicAdd(&s_h[run_d], run_n);
+    run_n = 0;
+  }
+  run_d = d;
+  ++run_n;
+}
+__device__ __forceinline__ void trim_flush(uint32_t *s_h, uint32_t run_d, uint32_t run_n, unsigned long long *__restrict__ hist) {
+  if (run_n) atomicAdd(&s_h[run_d], run_n);
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < bjx_trim::kBins; k += kBlock)
+    if (s_h[k]) atomicAdd(&hist[k], (unsigned long long)s_h[k]);
+}
+// grid-stride over the state table.  newest != NULL (the first pass of a trim
+// with max_ips): newest[id] = max key of IP id's states, bit id of has[] set
+// (both zeroed before).  hist != NULL: hist[d] += the live states whose key is
+// under prefix and has digit p equal to d (kBins counters, zeroed before).
+__global__ __launch_bounds__(kBlock) void k_trim_hist_st(uint64_t st_cap, const StSlot *__restrict__ st, uint64_t n_ips,
+                                                         uint64_t prefix, uint32_t p, unsigned long long *__restrict__ newest,
+                                                         uint32_t *__restrict__ has, unsigned long long *__restrict__ hist) {
+  __shared__ uint32_t s_h[bjx_trim::kBins];
+  for (uint32_t k = threadIdx.x; k < bjx_trim::kBins; k += kBlock) s_h[k] = 0;
+  __syncthreads();
+  uint32_t run_d = 0, run_n = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < st_cap; i += (uint64_t)gridDim.x * kBlock) {
+    const StSlot v = st[i];
+    if (!st_survives(v, INT64_MIN, n_ips)) continue;  // (its IP id is below n_ips)
+    const uint64_t key = bjx_trim::key_of(v.start);
+    if (newest) {
+      const uint64_t id = (v.key >> 24) - 1;
+      // both only grow, so a plain read that already covers this state spares
+      // the atomic (an IP has many states; a stale read costs one atomic more)
+      if (newest[id] < key) atomicMax(&newest[id], (unsigned long long)key);
+      if (!((has[id >> 5] >> (id & 31)) & 1u)) atomicOr(&has[id >> 5], 1u << (id & 31));
+    }
+    if (hist && bjx_trim::under(key, prefix, p)) trim_count(s_h, bjx_trim::digit(key, p), run_d, run_n);
+  }
+  if (hist) trim_flush(s_h, run_d, run_n, hist);
+}
+// the same count over newest[], for the IPs whose bit in has[] is set
+__global__ __launch_bounds__(kBlock) void k_trim_hist_ip(uint64_t n_ips, const unsigned long long *__restrict__ newest,
+                                                         const uint32_t *__restrict__ has, uint64_t prefix, uint32_t p,
+                                                         unsigned long long *__restrict__ hist) {
+  __shared__ uint32_t s_h[bjx_trim::kBins];
+  for (uint32_t k = threadIdx.x; k < bjx_trim::kBins; k += kBlock) s_h[k] = 0;
+  __syncthreads();
+  uint32_t run_d = 0, run_n = 0;
+  for (uint64_t id = (uint64_t)blockIdx.x * kBlock + threadIdx.x; id < n_ips; id += (uint64_t)gridDim.x * kBlock) {
+    if (!((has[id >> 5] >> (id & 31)) & 1u)) continue;
+    const uint64_t key = newest[id];
+    if (bjx_trim::under(key, prefix, p)) trim_count(s_h, bjx_trim::digit(key, p), run_d, run_n);
+  }
+  trim_flush(s_h, run_d, run_n, hist);
+}
+// k_exp_mark, counting also what goes: cnt[0] += states kept, cnt[1] += live
+// states dropped (start < cutoff), cnt[2] += those of them with start >=
+// live_floor (one atomic each per block)
+__global__ __launch_bounds__(kBlock) void k_trim_mark(uint64_t st_cap, const StSlot *__restrict__ st, int64_t cutoff,
+                                                      int64_t live_floor, uint64_t n_ips, uint32_t *__restrict__ keep,
+                                                      unsigned long long *__restrict__ cnt) {
+  uint64_t kept = 0, gone = 0, live = 0, z = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < st_cap; i += (uint64_t)gridDim.x * blockDim.x) {
+    const StSlot v = st[i];
+    if (!st_survives(v, INT64_MIN, n_ips)) continue;
+    if (v.start >= cutoff) {
+      keep[(v.key >> 24) - 1] = 1u;  // every writer stores the same value
+      ++kept;
+    } else {
+      ++gone;
+      if (v.start >= live_floor) ++live;
+    }
+  }
+  block_sum2(kept, gone);
+  __syncthreads();  // block_sum2's shared words are read before they are written again
+  block_sum2(live, z);
+  if (threadIdx.x == 0 && kept) atomicAdd(&cnt[0], (unsigned long long)kept);
+  if (threadIdx.x == 0 && gone) atomicAdd(&cnt[1], (unsigned long long)gone);
+  if (threadIdx.x == 0 && live) atomicAdd(&cnt[2], (unsigned long long)live);
+}
+
+// blocks of a grid-stride pass over n items (bjx_debug_set_trim_grid lowers the cap)
+unsigned trim_grid(const bjx_engine *e, uint64_t n) {
+  const uint64_t cap = e->dbg_trim_grid ? e->dbg_trim_grid : 2048;
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(grid_for(n), cap));
+}
+
+// The selection (the engine lock held).  A bound the counters already meet
+// needs no pass: counters[2] counts the claimed slots, which are never fewer
+// than the live states, and counters[0] the IPs.
+void trim_select_locked(bjx_engine *e, const bjx_trim_budget *b, bjx_trim::Picked *P) {
+  if (const char *why = bjx_trim::check_budget(b)) throw BjxError(BJX_ERR_ARG, std::string("bjx_state_trim: ") + why);
+  if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_trim between bjx_match_batch and its bjx_finish_batch");
+  HIP_OK(hipDeviceSynchronize());  // the tables as the last batch left them
+  State &S = e->S;
+  hipStream_t st = e->stream;
+  read_counters(e);
+  const uint64_t n_ips = e->host_counters[0], n_st = e->host_counters[2];
+  if (n_ips >= 0x7FFFFFFFull) throw BjxError(BJX_ERR_CAPACITY, "more than 2^31 distinct IPs");
+  const bool want_st = b->max_states && n_st > b->max_states, want_ip = b->max_ips && n_ips > b->max_ips;
+  bjx_trim::Cut c_st, c_ip;
+  double ms = 0;
+  if (want_st || want_ip) {
+    using namespace bjx_trim;
+    SnapEvents E;
+    E.create();
+    ExpAlloc tmp;
+    unsigned long long *newest = want_ip ? tmp.get<unsigned long long>(n_ips + 1) : nullptr;
+    uint32_t *has = want_ip ? tmp.get<uint32_t>(n_ips / 32 + 1) : nullptr;
+    unsigned long long *hist = tmp.get<unsigned long long>(2 * kBins);
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_trim: no device memory for the selection");
+    std::vector<uint64_t> h(2 * kBins);
+    Select sel[2];  // 0: over the states, 1: over the IPs' newest starts
+    bool open[2] = {want_st, want_ip};
+    const uint64_t bound[2] = {b->max_states, b->max_ips};
+    Cut *cut[2] = {&c_st, &c_ip};
+    HIP_OK(hipEventRecord(E.ev[0], st));
+    if (want_ip) {
+      HIP_OK(hipMemsetAsync(newest, 0, (n_ips + 1) * 8, st));
+      HIP_OK(hipMemsetAsync(has, 0, (n_ips / 32 + 1) * 4, st));
+    }
+    for (uint32_t p = 0; p < kDigits && (open[0] || open[1]); ++p) {
+      HIP_OK(hipMemsetAsync(hist, 0, 2 * kBins * 8, st));
+      if (open[0] || (p == 0 && want_ip)) {
+        hipLaunchKernelGGL(k_trim_hist_st, dim3(trim_grid(e, e->st_cap)), dim3(kBlock), 0, st, e->st_cap, S.st, n_ips, sel[0].prefix,
+                           p, p == 0 ? newest : nullptr, has, open[0] ? hist : nullptr);
+        HIP_OK(hipGetLastError());
+      }
+      if (open[1]) {
+        hipLaunchKernelGGL(k_trim_hist_ip, dim3(trim_grid(e, n_ips)), dim3(kBlock), 0, st, n_ips, newest, has, sel[1].prefix, p,
+                           hist + kBins);
+        HIP_OK(hipGetLastError());
+      }
+      HIP_OK(hipMemcpyAsync(h.data(), hist, 2 * kBins * 8, hipMemcpyDeviceToHost, st));
+      HIP_OK(hipStreamSynchronize(st));
+      for (int w = 0; w < 2; ++w) {
+        if (!open[w]) continue;
+        const uint64_t *hw = h.data() + w * kBins;
+        if (p == 0) {  // the first histogram counts every value: |V|
+          uint64_t total = 0;
+          for (uint32_t d = 0; d < kBins; ++d) total += hw[d];
+          if (unbounded(bound[w], total)) { open[w] = false; continue; }
+          sel[w].rank = bound[w] + 1;
+        }
+        if (!step(&sel[w], hw)) throw BjxError(BJX_ERR_DEVICE, "internal: trim histogram below the rank");
+        if (sel[w].done()) {
+          *cut[w] = cut_after(value_of(sel[w].prefix));
+          open[w] = false;
+        }
+      }
+    }
+    HIP_OK(hipEventRecord(E.ev[1], st));
+    HIP_OK(hipStreamSynchronize(st));
+    ms = E.ms(0, 1);
+  }
+  *P = bjx_trim::pick(b->floor_cutoff_ns, c_st, c_ip);
+  P->select_ms = ms;
+}
+
+// The trim at a cutoff (the engine lock held): the expiry with the trim's
+// counts, its no-op rule and its dry run.  R's cutoff, bound, budget_met and
+// select_ms are the caller's.
+void trim_apply_locked(bjx_engine *e, int64_t cutoff, int64_t live_floor, uint32_t flags, bjx_trim_stats *R) {
+  if (flags & ~(uint32_t)BJX_TRIM_DRY_RUN) throw BjxError(BJX_ERR_ARG, "bjx_state_trim: budget: unknown flag bits");
+  if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_trim between bjx_match_batch and its bjx_finish_batch");
+  HIP_OK(hipDeviceSynchronize());  // nothing of an earlier batch may land after the rebuild
+  State &S = e->S;
+  hipStream_t st = e->stream;
+  read_counters(e);
+  const uint64_t n_ips = e->host_counters[0], used = e->host_counters[1], n_st = e->host_counters[2];
+  if (n_ips >= 0x7FFFFFFFull) throw BjxError(BJX_ERR_CAPACITY, "more than 2^31 distinct IPs");
+  R->states_before = n_st; R->ips_before = n_ips;
+  R->states_dropped = R->states_dropped_live = R->ips_dropped = 0;
+  R->arena_bytes_before = R->arena_bytes_after = used;
+  R->device_bytes_before = R->device_bytes_after = state_device_bytes(e->ip_cap, e->st_cap, S.arena_cap);
+  R->device_ms = 0;
+  if (cutoff == INT64_MIN || !n_st) return;  // no start is below it / no state
+
+  SnapEvents E;
+  E.create();
+  ExpAlloc tmp;
+  Kept K(tmp, n_ips);
+  if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_trim: no device memory for the scan buffers");
+  unsigned long long gone = 0, live = 0;
+  e->chk.ensure(8);
+  HIP_OK(hipEventRecord(E.ev[0], st));
+  HIP_OK(hipMemsetAsync(K.keep, 0, (n_ips + 1) * 4, st));
+  HIP_OK(hipMemsetAsync(e->chk.p, 0, 32, st));
+  hipLaunchKernelGGL(k_trim_mark, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st, e->st_cap,
+                     S.st, cutoff, live_floor, n_ips, K.keep, e->chk.p);
+  HIP_OK(hipGetLastError());
+  hipLaunchKernelGGL(k_exp_len, dim3(grid_for(n_ips + 1)), dim3(kBlock), 0, st, n_ips, K.keep, S.ip_len, K.klen);
+  HIP_OK(hipGetLastError());
+  pin_get(e, &gone, e->chk.p + 1, 8);  // land with scan_kept's reads
+  pin_get(e, &live, e->chk.p + 2, 8);
+  scan_kept(e, K, n_ips, used, e->st_cap, E.ev[1], "internal: trim counts exceed the tables");
+  R->device_ms = E.ms(0, 1);
+  if (!gone) return;  // the tables were only read
+  R->states_dropped = gone;
+  R->states_dropped_live = live;
+  R->ips_dropped = n_ips - K.ips;
+  R->arena_bytes_after = K.bytes;
+  if (flags & BJX_TRIM_DRY_RUN) return;
+  e->counters_fresh = false;
+  rebuild_kept(e, K, n_ips, used, E.ev[2], E.ev[3], "bjx_state_trim: no device memory for the new tables (state unchanged)",
+               [&](NewTables &nw) {
+                 hipLaunchKernelGGL(k_exp_st, dim3(grid_for(e->st_cap)), dim3(kBlock), 0, st, e->st_cap, S.st, cutoff, n_ips, K.nid,
+                                    nw.st, nw.st_cap - 1);
+               });
+  R->device_bytes_after = state_device_bytes(e->ip_cap, e->st_cap, S.arena_cap);
+  R->device_ms += E.ms(2, 3);
+}
+
+}  // namespace
+
+int bjx_trim_select(bjx_engine *e, const bjx_trim_budget *b, bjx_trim::Picked *out) {
+  return guarded(e, [&]() -> int {
+    trim_select_locked(e, b, out);
+    return BJX_OK;
+  });
+}
+
+int bjx_trim_apply(bjx_engine *e, int64_t cutoff_ns, int64_t live_floor_ns, uint32_t flags, bjx_trim_stats *out) {
+  return guarded(e, [&]() -> int {
+    bjx_trim_stats R{};
+    trim_apply_locked(e, cutoff_ns, live_floor_ns, flags, &R);
+    if (out) *out = R;
+    return BJX_OK;
+  });
+}
+
+// Trim: the selection, then the expiry at the cutoff it found, under one hold
+// of the engine lock.
+extern "C" int bjx_state_trim(bjx_engine *e, const bjx_trim_budget *b, bjx_trim_stats *out) {
+  return guarded(e, [&]() -> int {
+    bjx_trim::Picked P;
+    trim_select_locked(e, b, &P);
+    bjx_trim_stats R{};
+    trim_apply_locked(e, P.cutoff, b->floor_cutoff_ns, b->flags, &R);
+    R.cutoff_ns = P.cutoff; R.bound = P.bound; R.budget_met = P.budget_met;
+    R.select_ms = P.select_ms;
+    R.device_ms += P.select_ms;
+    if (out) *out = R;
+    return BJX_OK;
+  });
+}

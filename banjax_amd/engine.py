@@ -480,6 +480,26 @@ class Engine:
                     "state_remove")
         return {k: getattr(st, k) for k, _ in _lib.RemoveStats._fields_}
 
+    _trim = "bjx_state_trim"
+
+    def state_trim(self, max_states: int = 0, max_ips: int = 0, floor_cutoff_ns: int = INT64_MIN,
+                   dry_run: bool = False) -> dict:
+        """Evict the oldest states until at most max_states states and max_ips
+        IPs are left (0: no bound); states that started before floor_cutoff_ns
+        always go (bjx_state_trim; banjax_amd/state_trim.py is its model).  The
+        cutoff is found on the device and the expiry at that cutoff follows;
+        nothing to drop leaves the engine exactly as it was.  dry_run: the
+        cutoff and the counts as the real call would report them, nothing
+        changed.  Returns the bjx_trim_stats fields."""
+        bud = _lib.TrimBudget(max_states, max_ips, floor_cutoff_ns, _lib.TRIM_DRY_RUN if dry_run else 0, 0)
+        st = _lib.TrimStats()
+        self._check(getattr(_lib.lib(), self._trim)(self._h, C.byref(bud), C.byref(st)), "state_trim")
+        return {k: getattr(st, k) for k, _ in _lib.TrimStats._fields_}
+
+    def debug_set_trim_grid(self, max_blocks: int):
+        """Test hook: the block cap of state_trim's counting passes (0 = default)."""
+        self._check(_lib.lib().bjx_debug_set_trim_grid(self._h, max_blocks), "debug_set_trim_grid")
+
     _rule_stats = "bjx_"
 
     def rule_stats(self, total: bool = False) -> dict:
@@ -648,6 +668,9 @@ class Node:
 
     _remove = "bjx_node_state_remove"
     state_remove = Engine.state_remove  # every shard gets the filter and the whole list; stats summed
+
+    _trim = "bjx_node_state_trim"
+    state_trim = Engine.state_trim  # the budget per engine, one cutoff for the node (the engines' largest); stats summed
 
     _rule_stats = "bjx_node_"
     rule_stats = Engine.rule_stats  # the engines' arrays summed; engine(k).rule_stats() has engine k's own

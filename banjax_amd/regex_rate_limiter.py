@@ -575,6 +575,17 @@ class RegexRateLimiter:
         with self._mu:
             return self.engine.state_expire(expire_cutoff_ns(now_ns, self._snap.config))
 
+    def bound_states(self, now_ns: int, max_states: int = 0, max_ips: int = 0, dry_run: bool = False) -> dict:
+        """Keep the rate-limit state within max_states states and max_ips IPs
+        (0: no bound) by evicting the oldest windows first (Engine.state_trim),
+        with expire_states' cutoff as the floor: what an expiry would drop goes
+        anyway, and states_dropped_live counts the evictions above it, which
+        can change a later result.  Meant to be called after every batch; within
+        the budget it moves nothing.  Returns the trim stats."""
+        with self._mu:
+            return self.engine.state_trim(max_states=max_states, max_ips=max_ips,
+                                          floor_cutoff_ns=expire_cutoff_ns(now_ns, self._snap.config), dry_run=dry_run)
+
     def export_states(self, now_ns: Optional[int] = None) -> bytes:
         """The rate-limit state as a snapshot blob (Engine.state_export) for the
         host to write out on shutdown.  With now_ns only what expire_states(now_ns)

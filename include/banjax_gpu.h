@@ -528,6 +528,89 @@ int bjx_state_query_nets(bjx_engine *e, const bjx_state_filter *f, const bjx_str
                          bjx_state_rows *out, const uint64_t **net_ips);
 int bjx_state_remove_nets(bjx_engine *e, const bjx_state_filter *f, const bjx_str *nets, size_t n_nets,
                           bjx_remove_stats *out);
+/* ---- Trim: evict the oldest state down to a budget.  Under a flood of
+   distinct source addresses the states are fresh, so the trip-transparent
+   cutoff of bjx_state_expire frees nothing, and the host cannot know which
+   cutoff frees enough: the distribution of interval_start_ns lives in HBM.
+   This call answers "keep this engine's state under max_states states and
+   max_ips IPs, and lose the least recent information possible": it finds the
+   cutoff on the device and expires at it.
+
+   Which states count: those with valid != 0 -- exactly what bjx_state_export
+   writes and bjx_state_query counts.
+
+   The cutoff.  For a multiset V of int64 and a bound k, cut(V, k) is the
+   smallest C with #{v in V : v >= C} <= k: INT64_MIN when k == 0 (no bound)
+   or |V| <= k, else v + 1 for the (k + 1)-th largest value v of V, saturating
+   at INT64_MAX.  With
+       C_states = cut(the starts of all states, max_states)
+       C_ips    = cut({the newest start of each held IP}, max_ips)
+   the cutoff is C = max(floor_cutoff_ns, C_states, C_ips).
+
+   The trim is bjx_state_expire(C): every state with interval_start_ns < C
+   goes and every IP left without a state goes too; the survivors keep their
+   first-seen order under dense ids; the tables are rebuilt by the expiry's
+   path with its sizing rule; the new tables are allocated before the old ones
+   are freed (BJX_ERR_NOMEM leaves the state untouched and usable); rehashes
+   does not count a trim.  Afterwards everything observable equals an engine
+   that imported a snapshot of the survivors.
+
+   Ties: states that share a start go or stay together, so the result is a
+   function of the logical state alone (never of slot layout) and may hold
+   fewer states than the budget allows.  Saturated case: when more than k
+   values equal INT64_MAX, C = INT64_MAX, those states stay and budget_met is
+   0; in every other case budget_met is 1.
+
+   bound says what set C: BJX_TRIM_BY_IPS if C_ips == C and C_ips > INT64_MIN,
+   else BJX_TRIM_BY_STATES if C_states == C and C_states > INT64_MIN, else
+   BJX_TRIM_BY_FLOOR if floor_cutoff_ns > INT64_MIN, else BJX_TRIM_BY_NONE.
+
+   states_dropped_live counts the dropped states with interval_start_ns >=
+   floor_cutoff_ns.  A host that passes the trip-transparent cutoff of
+   bjx_state_expire as the floor reads here how many evictions were not
+   transparent: forgetting such a state can turn a later InsideInterval event
+   into FirstTime, restart its count and so delay or lose a trip (see the
+   expiry's contract for what a forgotten state changes).  states_dropped
+   counts the valid states that went.
+
+   When no state would be dropped the engine is left exactly as it was: no
+   rebuild runs, no table changes size and the stats' after equals their
+   before (as bjx_state_remove, unlike the expiry: the trim is meant to be
+   called after every batch).  A budget the counters already meet costs no pass
+   over the tables.
+
+   BJX_TRIM_DRY_RUN computes cutoff_ns, bound, budget_met, the three dropped
+   counts and arena_bytes_after exactly as the real call would report them and
+   changes nothing; device_bytes_after = device_bytes_before.
+
+   BJX_ERR_ARG: a NULL handle or b, unknown flag bits, a call between
+   bjx_match_batch and its bjx_finish_batch* (the node call waits for the node
+   batch instead, as expiry does).  out may be NULL.  Takes the engine lock
+   like the other bjx_state_* calls.  Temporary device memory of the
+   selection: 8 bytes and one bit per held IP (only with max_ips) and 128 KiB
+   of digit counters; no per-state temporary -- the state table is read in
+   place, at most five times. */
+enum bjx_trim_flags { BJX_TRIM_DRY_RUN = 1 };
+enum bjx_trim_bound { BJX_TRIM_BY_NONE = 0, BJX_TRIM_BY_FLOOR = 1, BJX_TRIM_BY_STATES = 2, BJX_TRIM_BY_IPS = 3 };
+typedef struct bjx_trim_budget {   /* 32 B */
+  uint64_t max_states;      /* keep at most this many states; 0: no bound */
+  uint64_t max_ips;         /* keep at most this many IPs;    0: no bound */
+  int64_t floor_cutoff_ns;  /* states that started before this always go (INT64_MIN: none) */
+  uint32_t flags;           /* bjx_trim_flags */
+  uint32_t _pad;
+} bjx_trim_budget;
+typedef struct bjx_trim_stats {    /* 104 B */
+  int64_t cutoff_ns;                 /* the cutoff C that was (or would be) applied */
+  uint32_t bound;                    /* enum bjx_trim_bound: what set C */
+  uint32_t budget_met;               /* 0 only in the saturated case above */
+  uint64_t states_before, states_dropped, states_dropped_live;
+  uint64_t ips_before, ips_dropped;
+  uint64_t arena_bytes_before, arena_bytes_after;
+  uint64_t device_bytes_before, device_bytes_after;  /* as bjx_state_stats.device_bytes */
+  double select_ms;                  /* HIP events around finding C */
+  double device_ms;                  /* select + mark/scan + rebuild, copies excluded */
+} bjx_trim_stats;
+int bjx_state_trim(bjx_engine *e, const bjx_trim_budget *b, bjx_trim_stats *out);
 /* RegexRateLimitStates.String(): "ip:\n\trule:\n\t\t{hits start}\n" blocks, IPs in
    first-seen order.  Returns the full length (writes at most cap bytes). */
 size_t bjx_state_dump(bjx_engine *e, char *out, size_t cap);
@@ -765,6 +848,20 @@ int bjx_node_state_query_nets(bjx_node *n, const bjx_state_filter *f, const bjx_
                               bjx_state_rows *out, const uint64_t **net_ips);
 int bjx_node_state_remove_nets(bjx_node *n, const bjx_state_filter *f, const bjx_str *nets, size_t n_nets,
                                bjx_remove_stats *out);
+/* bjx_state_trim over the node.  The budget is per engine (each engine's HBM
+   is its own); the node keeps one cutoff, so that the node as a whole "forgot
+   everything before C".  Waits for the node batch, as bjx_node_state_expire
+   does; runs the selection on every engine, takes C = the largest of their
+   cutoffs and applies C on every engine (a trim with C as the floor and no
+   bounds).  Counts and bytes are summed; cutoff_ns = C; bound is that of the
+   engine that gave C (the lowest engine index among several); budget_met is
+   the AND over the engines; select_ms and device_ms are the slowest engine's;
+   states_dropped_live is counted against the caller's floor, not against C.
+   A selection that fails on one engine is still run on the others and nothing
+   is applied; when applying, every engine is asked even when one fails.  The
+   first failure is returned and the call is idempotent, so the caller repeats
+   it, as with bjx_node_state_remove.  out may be NULL. */
+int bjx_node_state_trim(bjx_node *n, const bjx_trim_budget *b, bjx_trim_stats *out);
 /* bjx_batch_rule_stats / bjx_rule_stats_total / bjx_rule_stats_reset over the
    node: the engines' arrays summed (engine k counted chunk k's lines),
    n_lines summed, device_ms the slowest engine's (totals: those summed). */

@@ -70,6 +70,10 @@ int bjx_debug_set_slot_cache(bjx_engine *e, int on);
    k_bucket_apply can run at without a table of 2^(16 + L) slots.  Unused, the
    same kernels run with the same arguments as without the hook. */
 int bjx_debug_set_bucket_bits(bjx_engine *e, uint32_t bits);
+/* Test hook: the counting passes of bjx_state_trim (over the state table and
+   over the per-IP newest starts) launch at most max_blocks blocks (0 = the
+   default cap), so that their grid-stride loops wrap on small inputs. */
+int bjx_debug_set_trim_grid(bjx_engine *e, uint32_t max_blocks);
 /* Test hook: the state-table slot index each of n (IP, rule name) states
    occupies, found as bjx_state_get finds it (hash, probe chain, IP bytes,
    then the state's key), in one launch for the whole list; -1 where there is
