@@ -114,6 +114,7 @@ EXPORTS = [
     "bjx_state_remove", "bjx_node_state_remove",
     "bjx_state_query_nets", "bjx_node_state_query_nets", "bjx_state_remove_nets", "bjx_node_state_remove_nets",
     "bjx_state_trim", "bjx_node_state_trim",
+    "bjx_state_query_groups", "bjx_node_state_query_groups",
     "bjx_batch_rule_stats", "bjx_rule_stats_total", "bjx_rule_stats_reset",
     "bjx_node_batch_rule_stats", "bjx_node_rule_stats_total", "bjx_node_rule_stats_reset",
 ]
@@ -184,6 +185,29 @@ class TrimStats(C.Structure):
                                           "ips_dropped", "arena_bytes_before", "arena_bytes_after",
                                           "device_bytes_before", "device_bytes_after")] + \
                [("select_ms", C.c_double), ("device_ms", C.c_double)]
+
+
+GROUPS_BY_IPS, GROUPS_BY_STATES, GROUPS_BY_HITS = 0, 1, 2
+GROUPS_MAX_ROWS = 65536
+
+
+class GroupSpec(C.Structure):
+    """bjx_group_spec: the prefix lengths, the order and the cut of a bjx_state_query_groups (24 B)."""
+    _fields_ = [("v4_bits", C.c_uint32), ("v6_bits", C.c_uint32), ("order", C.c_uint32), ("limit", C.c_uint32),
+                ("min_ips", C.c_uint64)]
+
+
+class GroupRow(C.Structure):
+    """bjx_group_row: one network of the answer (56 B)."""
+    _fields_ = [("addr", C.c_uint8 * 16), ("family", C.c_uint32), ("bits", C.c_uint32), ("n_ips", C.c_uint64),
+                ("n_states", C.c_uint64), ("hits_sum", C.c_int64), ("newest_start_ns", C.c_int64)]
+
+
+class StateGroups(C.Structure):
+    """bjx_state_groups: counts and the first rows of a bjx_state_query_groups (72 B)."""
+    _fields_ = [(k, C.c_uint64) for k in ("n_matched", "n_ips_matched", "n_ips_unparsed", "n_states_unparsed", "n_groups",
+                                            "n_groups_min", "n_rows")] + \
+               [("rows", C.POINTER(GroupRow)), ("device_ms", C.c_double)]
 
 
 class RuleStat(C.Structure):
@@ -369,6 +393,11 @@ def lib():
     for name in ("bjx_state_trim", "bjx_node_state_trim"):
         f = getattr(L, name)
         f.restype, f.argtypes = C.c_int, [vp, C.POINTER(TrimBudget), C.POINTER(TrimStats)]
+    for name in ("bjx_state_query_groups", "bjx_node_state_query_groups"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(GroupSpec), C.POINTER(StateGroups)]
+    L.bjx_debug_groups_tile.restype = C.c_uint32
+    L.bjx_debug_groups_tile.argtypes = []
     L.bjx_debug_set_trim_grid.restype = C.c_int
     L.bjx_debug_set_trim_grid.argtypes = [vp, C.c_uint32]
     for pre in ("bjx_", "bjx_node_"):

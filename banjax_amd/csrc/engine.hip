@@ -49,6 +49,7 @@
 #include "state_remove.h"
 #include "state_nets.h"
 #include "state_trim.h"
+#include "state_groups.h"
 
 using namespace bjx;
 
@@ -5239,6 +5240,7 @@ struct bjx_engine {
   HostBuf<bjx_state_row> qry_rows;  // bjx_state_query: the last answer (valid until the next query)
   HostBuf<uint8_t> qry_bytes;
   std::vector<uint64_t> qry_net_ips;  // bjx_state_query_nets: the last answer's net_ips
+  std::vector<bjx_group_row> grp_rows;  // bjx_state_query_groups: the last answer's rows
 
   // per-rule counts of the batches closed with BJX_RULE_STATS (rule_stats.h);
   // nothing here is allocated or created before the first such batch

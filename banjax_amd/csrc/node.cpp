@@ -48,6 +48,7 @@
 #include "state_remove.h"
 #include "state_trim.h"
 #include "state_nets.h"
+#include "state_groups.h"
 
 namespace {
 
@@ -130,6 +131,7 @@ struct bjx_node {
   std::vector<bjx_state_row> q_rows;
   std::vector<uint8_t> q_bytes;
   std::vector<uint64_t> q_net_ips;  // and of the last bjx_node_state_query_nets, the summed net_ips
+  std::vector<bjx_group_row> g_rows;  // the last bjx_node_state_query_groups' rows
   // per-rule counts (BJX_RULE_STATS): the engines' arrays summed, for the last
   // batch and over every flagged batch since its ruleset came into use
   bool rs_counted = false;
@@ -1177,6 +1179,36 @@ extern "C" int bjx_node_state_trim(bjx_node *n, const bjx_trim_budget *b, bjx_tr
     if (first_rc != BJX_OK) fail(first_rc, first_msg);
     t.cutoff_ns = P.cutoff; t.bound = P.bound; t.budget_met = P.budget_met;
     if (out) *out = t;
+    return BJX_OK;
+  });
+}
+
+// every shard's complete group list, merged by key on the host; min_ips, the
+// order and the limit only then (state_groups.h: merge, finish)
+extern "C" int bjx_node_state_query_groups(bjx_node *n, const bjx_state_filter *f, const bjx_group_spec *g,
+                                           bjx_state_groups *out) {
+  if (!n || !f || !g || !out) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    memset(out, 0, sizeof *out);
+    if (const char *why = bjx_groups::check_filter(f)) fail(BJX_ERR_ARG, std::string("bjx_node_state_query_groups: ") + why);
+    if (const char *why = bjx_groups::check_spec(g)) fail(BJX_ERR_ARG, std::string("bjx_node_state_query_groups: ") + why);
+    const char *const too_many =
+        "bjx_node_state_query_groups: more than 2^24 groups on the shards together (use shorter prefixes or a narrower filter)";
+    std::vector<std::vector<bjx_groups::Rec>> lists(n->parts.size());
+    bjx_groups::Counts total;
+    uint64_t held = 0;
+    for (size_t k = 0; k < n->parts.size(); ++k) {
+      bjx_engine *e = n->parts[k].e;
+      bjx_groups::Counts c;
+      const int rc = bjx_groups_list(e, f, g, bjx_groups::kGroupsNodeMax - held, &lists[k], &c);
+      if (rc == BJX_ERR_CAPACITY) fail(rc, too_many);
+      if (rc != BJX_OK) fail(rc, "engine " + std::to_string(k) + ": " + bjx_engine_last_error(e));
+      held += lists[k].size();
+      bjx_groups::add(&total, c);
+    }
+    std::vector<bjx_groups::Rec> merged;
+    if (!bjx_groups::merge(lists, bjx_groups::kGroupsNodeMax, &merged)) fail(BJX_ERR_CAPACITY, too_many);
+    bjx_groups::finish(merged, *g, total, out, &n->g_rows);
     return BJX_OK;
   });
 }

@@ -2222,3 +2222,455 @@ extern "C" int bjx_state_trim(bjx_engine *e, const bjx_trim_budget *b, bjx_trim_
     return BJX_OK;
   });
 }
+
+// ---- groups: bjx_state_query_groups (the checks, the key of an address, the
+// group record, the rows' order, the node's merge: state_groups.h).  One pass
+// over the state table adds every selected state into a 32-byte record per
+// held IP (k_grp_scan: a state count, a hits sum, the newest start under the
+// trim's biased key; an IP has at most as many states as there are names, so
+// these atomics do not pile up).  One lane per held IP with a count then parses the
+// address in place, masks it and appends its key (k_grp_key).  The keys are
+// sorted through an index by the bits in which keys can differ -- the low
+// word, the high word, then the family bit when both families are present --
+// and laid out in that order (k_grp_sorted).  k_grp_heads marks the first key
+// of every run of equal keys, a scan numbers the runs, and k_grp_runs reduces
+// each run to one record: a block owns kGrpTile consecutive keys, a thread
+// sums its kGrpItems keys in registers run by run and adds each run to the
+// block's LDS record of that group; a group that lies inside the tile is then
+// stored plainly, and only the tile's first and last group, when they go on in
+// a neighbouring tile, are added to global memory -- so a /0 group of every
+// IP costs two global atomics a block, not one a member.  The records come out
+// in key order, which is the rows' tie order: min_ips is a stable compaction
+// (flags and a scan), the order a stable sort by the primary key alone.
+namespace {
+
+constexpr int kGrpItems = 4;                                // k_grp_runs: consecutive keys per thread
+constexpr uint32_t kGrpTile = kBlock * kGrpItems;           // keys per block of k_grp_runs
+static_assert(sizeof(bjx_group_row) == 56 && sizeof(bjx_group_spec) == 24, "the groups structs of the C ABI");
+// what the scan adds up per held IP: one 32-byte record, so that the three
+// atomics of a state fall into one cache line and k_grp_runs reads an IP's
+// values with one load (the scan itself runs at the rate of its atomics and
+// took the same time with three arrays: DESIGN.md §2 "Groups")
+struct GrpAcc {
+  unsigned long long hsum, newest;  // hits, wrapping; the newest start as bjx_groups::start_key
+  uint32_t cnt, _pad[3];            // selected states
+};
+static_assert(sizeof(GrpAcc) == 32, "GrpAcc is half a cache line");
+
+// grid-stride over the state table (k_rm_mark's shape); sel != NULL: only the
+// states of IPs with sel[id] set.  acc[] zeroed before; tot[0] += selected
+// states (one atomic per block)
+__global__ __launch_bounds__(kBlock) void k_grp_scan(uint64_t st_cap, const StSlot *__restrict__ st, QFilter F, uint64_t n_ips,
+                                                     uint32_t n_names, const uint32_t *__restrict__ sel,
+                                                     GrpAcc *__restrict__ acc, unsigned long long *__restrict__ tot) {
+  uint64_t n = 0, z = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < st_cap; i += (uint64_t)gridDim.x * blockDim.x) {
+    const StSlot v = st[i];
+    if (!rm_selected(v, F, n_ips, n_names, sel)) continue;  // (its IP id is below n_ips)
+    const uint64_t id = (v.key >> 24) - 1;
+    atomicAdd(&acc[id].cnt, 1u);
+    atomicAdd(&acc[id].hsum, (unsigned long long)v.hits);
+    const unsigned long long key = bjx_groups::start_key(v.start);
+    if (acc[id].newest < key) atomicMax(&acc[id].newest, key);  // it only grows: a read that covers this state spares the atomic
+    ++n;
+  }
+  block_sum2(n, z);
+  if (threadIdx.x == 0 && n) atomicAdd(&tot[0], (unsigned long long)n);
+}
+
+// One lane per held IP; every block runs the same number of passes
+// (block_alloc).  An IP with a count whose bytes parse gets entry k of the key
+// arrays: c_lo / c_hi the masked address, c_id its id with the family bit on
+// top, perm[k] = k.  ctr[1] += entries (block_alloc), ctr[2] += IPs with a
+// count, ctr[3] / ctr[4] += those that do not parse and their states,
+// ctr[5] += IPv6 entries (one atomic each per block)
+__global__ __launch_bounds__(kBlock) void k_grp_key(uint64_t n_ips, const GrpAcc *__restrict__ acc,
+                                                    const uint64_t *__restrict__ ip_off, const uint32_t *__restrict__ ip_len,
+                                                    const uint8_t *__restrict__ arena, uint64_t arena_used, uint32_t v4_bits,
+                                                    uint32_t v6_bits, uint64_t room, unsigned long long *__restrict__ ctr,
+                                                    uint64_t *__restrict__ c_lo, uint64_t *__restrict__ c_hi,
+                                                    uint32_t *__restrict__ c_id, uint32_t *__restrict__ perm) {
+  uint64_t has = 0, bad = 0, bad_st = 0, n6 = 0;
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n_ips; base += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t id = base + threadIdx.x;
+    const uint32_t c = id < n_ips ? acc[id].cnt : 0u;
+    bool ok = false;
+    uint32_t fam6 = 0;
+    uint64_t hi = 0, lo = 0;
+    if (c) {
+      ++has;
+      uint8_t a[16];
+      if (net_ip_addr(id, ip_off, ip_len, arena, arena_used, a)) {
+        ok = true;
+        bjx_groups::pack(a, v4_bits, v6_bits, &fam6, &hi, &lo);
+        n6 += fam6;
+      } else {
+        ++bad;
+        bad_st += c;
+      }
+    }
+    const uint64_t k = block_alloc(&ctr[1], ok ? 1 : 0);
+    if (ok && k < room) {
+      c_lo[k] = lo;
+      c_hi[k] = hi;
+      c_id[k] = (uint32_t)id | (fam6 << 31);
+      perm[k] = (uint32_t)k;
+    }
+  }
+  block_sum2(has, bad);
+  __syncthreads();  // block_sum2's shared words are read before they are written again
+  block_sum2(bad_st, n6);
+  if (threadIdx.x == 0 && has) atomicAdd(&ctr[2], (unsigned long long)has);
+  if (threadIdx.x == 0 && bad) atomicAdd(&ctr[3], (unsigned long long)bad);
+  if (threadIdx.x == 0 && bad_st) atomicAdd(&ctr[4], (unsigned long long)bad_st);
+  if (threadIdx.x == 0 && n6) atomicAdd(&ctr[5], (unsigned long long)n6);
+}
+// the next sort's key of entry perm[j]: the high word (what == 0) or the family bit
+__global__ void k_grp_word(uint64_t n, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ c_hi,
+                           const uint32_t *__restrict__ c_id, uint32_t what, uint64_t *__restrict__ out) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t q = perm[j];
+  out[j] = q < n ? (what ? (uint64_t)(c_id[q] >> 31) : c_hi[q]) : ~0ull;  // (a permutation of [0, n): always inside)
+}
+// the entries in sorted order
+__global__ void k_grp_sorted(uint64_t n, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ c_lo,
+                             const uint64_t *__restrict__ c_hi, const uint32_t *__restrict__ c_id, uint64_t *__restrict__ s_lo,
+                             uint64_t *__restrict__ s_hi, uint32_t *__restrict__ s_id) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t q = perm[j];
+  const bool in = q < n;  // (a permutation of [0, n): always inside)
+  s_lo[j] = in ? c_lo[q] : 0;
+  s_hi[j] = in ? c_hi[q] : 0;
+  s_id[j] = in ? c_id[q] : 0x7FFFFFFFu;  // (an id k_grp_runs does not follow)
+}
+// head[j] = 1 where sorted entry j begins a run of equal keys, over [0, n] (the last entry 0: the scan's total lands there)
+__global__ void k_grp_heads(uint64_t n, const uint64_t *__restrict__ s_lo, const uint64_t *__restrict__ s_hi,
+                            const uint32_t *__restrict__ s_id, uint32_t *__restrict__ head) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j > n) return;
+  if (j == n) { head[j] = 0; return; }
+  head[j] = j == 0 || s_lo[j] != s_lo[j - 1] || s_hi[j] != s_hi[j - 1] || ((s_id[j] ^ s_id[j - 1]) >> 31) ? 1u : 0u;
+}
+// Block b reduces sorted entries [b * kGrpTile, (b + 1) * kGrpTile) (the grid
+// is exactly the tiles).  gpos = the exclusive scan of head: entry j lies in
+// group gpos[j] + head[j] - 1.  out[] zeroed before; the entry that begins a
+// group writes its key.
+__global__ __launch_bounds__(kBlock) void k_grp_runs(uint64_t n, const uint64_t *__restrict__ s_lo, const uint64_t *__restrict__ s_hi,
+                                                     const uint32_t *__restrict__ s_id, const uint32_t *__restrict__ head,
+                                                     const uint32_t *__restrict__ gpos, uint64_t n_ips,
+                                                     const GrpAcc *__restrict__ acc, uint64_t n_groups,
+                                                     bjx_groups::Rec *__restrict__ out) {
+  __shared__ uint32_t l_ips[kGrpTile];
+  __shared__ unsigned long long l_st[kGrpTile], l_hits[kGrpTile], l_new[kGrpTile];
+  const uint64_t t0 = (uint64_t)blockIdx.x * kGrpTile;
+  if (t0 >= n) return;  // (the grid is exactly the tiles)
+  const uint64_t t1 = t0 + kGrpTile < n ? t0 + kGrpTile : n;
+  for (uint32_t k = threadIdx.x; k < kGrpTile; k += kBlock) {
+    l_ips[k] = 0;
+    l_st[k] = l_hits[k] = l_new[k] = 0;
+  }
+  __syncthreads();
+  const uint64_t g0 = (uint64_t)gpos[t0] + head[t0] - 1;  // the tile's first group (head[0] is 1)
+  uint64_t run = ~0ull;
+  uint32_t a_ips = 0;
+  unsigned long long a_st = 0, a_hits = 0, a_new = 0;
+  auto flush = [&]() {
+    const uint64_t l = run - g0;  // the tile holds at most kGrpTile groups
+    if (a_ips && l < kGrpTile) {
+      atomicAdd(&l_ips[l], a_ips);
+      atomicAdd(&l_st[l], a_st);
+      atomicAdd(&l_hits[l], a_hits);
+      atomicMax(&l_new[l], a_new);
+    }
+    a_ips = 0;
+    a_st = a_hits = a_new = 0;
+  };
+  const uint64_t j0 = t0 + (uint64_t)threadIdx.x * kGrpItems;
+#pragma unroll
+  for (int i = 0; i < kGrpItems; ++i) {
+    const uint64_t j = j0 + i;
+    if (j >= t1) break;
+    const uint32_t h = head[j], w = s_id[j], id = w & 0x7FFFFFFFu;
+    const uint64_t g = (uint64_t)gpos[j] + h - 1;
+    if (g != run) {
+      flush();
+      run = g;
+    }
+    if (h && g < n_groups) {
+      out[g].hi = s_hi[j];
+      out[g].lo = s_lo[j];
+      out[g].fam6 = w >> 31;
+    }
+    if (id < n_ips) {
+      const GrpAcc v = acc[id];
+      a_ips += 1;
+      a_st += v.cnt;
+      a_hits += v.hsum;
+      a_new = v.newest > a_new ? v.newest : a_new;
+    }
+  }
+  flush();
+  __syncthreads();
+  const uint64_t g1 = (uint64_t)gpos[t1 - 1] + head[t1 - 1] - 1;  // the tile's last group
+  const uint64_t n_local = g1 - g0 + 1;
+  const bool open_front = head[t0] == 0;           // the first group began in an earlier tile
+  const bool open_back = t1 < n && head[t1] == 0;  // the last group goes on in the next tile
+  for (uint64_t l = threadIdx.x; l < n_local && l < kGrpTile; l += kBlock) {
+    const uint64_t g = g0 + l;
+    if (g >= n_groups) continue;
+    if ((l == 0 && open_front) || (l == n_local - 1 && open_back)) {
+      atomicAdd((unsigned long long *)&out[g].n_ips, (unsigned long long)l_ips[l]);
+      atomicAdd((unsigned long long *)&out[g].n_states, l_st[l]);
+      atomicAdd((unsigned long long *)&out[g].hits, l_hits[l]);
+      atomicMax((unsigned long long *)&out[g].newest, l_new[l]);
+    } else {
+      out[g].n_ips = l_ips[l];
+      out[g].n_states = l_st[l];
+      out[g].hits = l_hits[l];
+      out[g].newest = l_new[l];
+    }
+  }
+}
+// ok[g] = 1 for the groups with n_ips >= min_ips, over [0, n_groups] (the last entry 0)
+__global__ void k_grp_ok(uint64_t n_groups, const bjx_groups::Rec *__restrict__ recs, uint64_t min_ips, uint32_t *__restrict__ ok) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g > n_groups) return;
+  ok[g] = g < n_groups && recs[g].n_ips >= min_ips ? 1u : 0u;
+}
+// the kept groups, still in key order: the primary key turned round (a
+// smaller word is an earlier row) and the group's index.  top: an upper bound
+// of the unsigned primaries, so that their words stay within its bits
+__global__ void k_grp_prim(uint64_t n_groups, const bjx_groups::Rec *__restrict__ recs, const uint32_t *__restrict__ ok,
+                           const uint32_t *__restrict__ pos, uint64_t room, uint32_t order, uint64_t top,
+                           uint64_t *__restrict__ prim, uint32_t *__restrict__ gi) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_groups || !ok[g]) return;
+  const uint64_t k = pos[g];
+  if (k >= room) return;  // (a scan of ok[]: always inside)
+  const bjx_groups::Rec r = recs[g];
+  const uint64_t v = order == BJX_GROUPS_BY_IPS ? r.n_ips : r.n_states;
+  prim[k] = order == BJX_GROUPS_BY_HITS ? bjx_query::key_desc((int64_t)r.hits) : (v <= top ? top - v : 0);
+  gi[k] = (uint32_t)g;
+}
+__global__ void k_grp_rows(uint64_t n_rows, const uint32_t *__restrict__ gi, uint64_t n_groups,
+                           const bjx_groups::Rec *__restrict__ recs, bjx_groups::Rec *__restrict__ rows) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rows) return;
+  const uint32_t g = gi[r];
+  rows[r] = g < n_groups ? recs[g] : bjx_groups::Rec{};  // (an index of a group: always inside)
+}
+
+// The query (the engine lock held by the caller's guarded()).  list == NULL:
+// the rows into e->grp_rows and *out.  list != NULL (the node): every group
+// in key order into *list, at most `room` of them, and the counts into *cnt.
+int groups_locked(bjx_engine *e, const bjx_state_filter *f, const bjx_group_spec *g, bjx_state_groups *out, uint64_t room,
+                  std::vector<bjx_groups::Rec> *list, bjx_groups::Counts *cnt) {
+  const std::string who = "bjx_state_query_groups";
+  if (out) memset(out, 0, sizeof *out);
+  if (list) list->clear();
+  if (cnt) *cnt = bjx_groups::Counts{};
+  if (const char *why = bjx_groups::check_filter(f)) throw BjxError(BJX_ERR_ARG, who + ": " + why);
+  if (const char *why = bjx_groups::check_spec(g)) throw BjxError(BJX_ERR_ARG, who + ": " + why);
+  if (e->batch_open) throw BjxError(BJX_ERR_ARG, who + " between bjx_match_batch and its bjx_finish_batch");
+  HIP_OK(hipDeviceSynchronize());  // the tables as the last batch left them
+  State &S = e->S;
+  hipStream_t st = e->stream;
+  SnapEvents E;
+  E.create();
+  read_counters(e);
+  const uint64_t n_ips = e->host_counters[0], used = e->host_counters[1], n_st = e->host_counters[2];
+  const uint32_t n_names = (uint32_t)e->names.size();
+  if (!list) e->grp_rows.clear();
+  QFilter F{f->min_hits, f->min_start_ns, f->max_start_ns, kNone, 0u};
+  if (f->name.ptr) {
+    auto it = e->name_ids.find(std::string(f->name.ptr, f->name.len));
+    if (it == e->name_ids.end()) return BJX_OK;  // never interned: no state can carry it
+    F.name = it->second;
+  }
+  if (bjx_query::empty_window(*f) || !n_ips || !n_st || !n_names) return BJX_OK;
+  if (n_ips >= 0x7FFFFFFFull) throw BjxError(BJX_ERR_CAPACITY, who + ": 2^31 distinct IPs or more");
+  bjx_remove::List L;  // the filter's ip as a list of one (k_rm_ips finds it)
+  bjx_remove::pack(*f, nullptr, 0, &L);
+
+  ExpAlloc tmp;
+  GrpAcc *d_acc = tmp.get<GrpAcc>(n_ips + 1);
+  unsigned long long *d_ctr = tmp.get<unsigned long long>(8);
+  uint32_t *sel = L.restrict ? tmp.get<uint32_t>(n_ips + 1) : nullptr;
+  const uint64_t off_bytes = ((uint64_t)L.n_entries() + 1) * 4;
+  const uint64_t list_bytes = L.restrict ? off_bytes + L.bytes.size() : 0;
+  uint8_t *d_list = L.restrict ? tmp.get<uint8_t>(((list_bytes + 3) & ~3ull) + 16) : nullptr;
+  if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, who + ": no device memory for the per-IP sums");
+  if (L.restrict) {
+    std::vector<uint8_t> img(list_bytes);
+    memcpy(img.data(), L.off.data(), off_bytes);
+    if (!L.bytes.empty()) memcpy(img.data() + off_bytes, L.bytes.data(), L.bytes.size());
+    snap_copy_in(e, d_list, img.data(), list_bytes);  // one upload; waits for the stream
+  }
+  double ms = 0;
+
+  // 1. the per-IP sums
+  HIP_OK(hipEventRecord(E.ev[0], st));
+  HIP_OK(hipMemsetAsync(d_ctr, 0, 64, st));
+  HIP_OK(hipMemsetAsync(d_acc, 0, (n_ips + 1) * sizeof(GrpAcc), st));
+  if (L.restrict) {
+    HIP_OK(hipMemsetAsync(sel, 0, (n_ips + 1) * 4, st));
+    hipLaunchKernelGGL(k_rm_ips, dim3(grid_for(L.sel_count)), dim3(kBlock), 0, st, L.sel_first, L.sel_count,
+                       reinterpret_cast<const uint32_t *>(d_list), d_list + off_bytes, e->dbg_hash_mask, S.ip, S.ip_mask, n_ips, S.ip_off,
+                       S.ip_len, S.arena, used, sel);
+    HIP_OK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_grp_scan, dim3((unsigned)std::min<uint64_t>(grid_for(e->st_cap), 8192)), dim3(kBlock), 0, st, e->st_cap, S.st, F,
+                     n_ips, n_names, sel, d_acc, d_ctr);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord(E.ev[1], st));
+  unsigned long long matched = 0;
+  pin_get(e, &matched, d_ctr, 8);
+  pin_sync(e);
+  ms += E.ms(0, 1);
+  if (matched > n_st) throw BjxError(BJX_ERR_DEVICE, "internal: groups counts disagree with the tables");
+  bjx_groups::Counts C;
+  C.n_matched = matched;
+  auto done = [&]() {
+    C.device_ms = ms;
+    if (cnt) *cnt = C;
+    if (out) {
+      out->n_matched = C.n_matched; out->n_ips_matched = C.n_ips_matched;
+      out->n_ips_unparsed = C.n_ips_unparsed; out->n_states_unparsed = C.n_states_unparsed;
+      out->device_ms = ms;
+    }
+    return BJX_OK;
+  };
+  if (!matched) return done();
+
+  // 2. the keys of the IPs with a count
+  const uint64_t key_room = std::min<uint64_t>(n_ips, matched);  // an entry is an IP with a selected state
+  uint64_t *c_lo = tmp.get<uint64_t>(key_room), *c_hi = tmp.get<uint64_t>(key_room);
+  uint64_t *w0 = tmp.get<uint64_t>(key_room), *w1 = tmp.get<uint64_t>(key_room);
+  uint32_t *c_id = tmp.get<uint32_t>(key_room), *p0 = tmp.get<uint32_t>(key_room), *p1 = tmp.get<uint32_t>(key_room);
+  uint32_t *head = tmp.get<uint32_t>(key_room + 1), *gpos = tmp.get<uint32_t>(key_room + 1);
+  if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, who + ": no device memory for the keys");
+  HIP_OK(hipEventRecord(E.ev[0], st));
+  hipLaunchKernelGGL(k_grp_key, dim3((unsigned)std::min<uint64_t>(grid_for(n_ips), 8192)), dim3(kBlock), 0, st, n_ips, d_acc, S.ip_off,
+                     S.ip_len, S.arena, used, g->v4_bits, g->v6_bits, key_room, d_ctr, c_lo, c_hi, c_id, p0);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord(E.ev[1], st));
+  unsigned long long got[5] = {};  // entries, IPs with a count, unparsed IPs, their states, IPv6 entries
+  pin_get(e, got, d_ctr + 1, sizeof got);
+  pin_sync(e);
+  ms += E.ms(0, 1);
+  const uint64_t n = got[0];
+  if (n > key_room || got[1] > n_ips || n + got[2] != got[1] || got[3] > matched || got[4] > n)
+    throw BjxError(BJX_ERR_DEVICE, "internal: groups keys disagree with the counts");
+  C.n_ips_matched = got[1];
+  C.n_ips_unparsed = got[2];
+  C.n_states_unparsed = got[3];
+  if (!n) return done();
+
+  // 3. sort through the index, the low word first; the runs; one record a run
+  const bjx_groups::SortBits B = bjx_groups::sort_bits(g->v4_bits, g->v6_bits);
+  uint32_t *perm = p0, *spare = p1;
+  HIP_OK(hipEventRecord(E.ev[0], st));
+  auto sort_by = [&](const uint64_t *keys, int b0, int b1) {
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, keys, w1, perm, spare, (int)n, b0, b1, st); });
+    std::swap(perm, spare);
+  };
+  if (B.lo_end > B.lo_begin) sort_by(c_lo, B.lo_begin, B.lo_end);
+  if (B.hi_end > B.hi_begin && got[4]) {
+    hipLaunchKernelGGL(k_grp_word, dim3(grid_for(n)), dim3(kBlock), 0, st, n, perm, c_hi, c_id, 0u, w0);
+    HIP_OK(hipGetLastError());
+    sort_by(w0, B.hi_begin, B.hi_end);
+  }
+  if (got[4] && got[4] < n) {  // both families: the family bit above everything
+    hipLaunchKernelGGL(k_grp_word, dim3(grid_for(n)), dim3(kBlock), 0, st, n, perm, c_hi, c_id, 1u, w0);
+    HIP_OK(hipGetLastError());
+    sort_by(w0, 0, 1);
+  }
+  uint64_t *s_lo = w0, *s_hi = w1;
+  uint32_t *s_id = spare;
+  hipLaunchKernelGGL(k_grp_sorted, dim3(grid_for(n)), dim3(kBlock), 0, st, n, perm, c_lo, c_hi, c_id, s_lo, s_hi, s_id);
+  HIP_OK(hipGetLastError());
+  hipLaunchKernelGGL(k_grp_heads, dim3(grid_for(n + 1)), dim3(kBlock), 0, st, n, s_lo, s_hi, s_id, head);
+  HIP_OK(hipGetLastError());
+  cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, head, gpos, (int)(n + 1), st); });
+  HIP_OK(hipEventRecord(E.ev[1], st));
+  uint32_t n_groups32 = 0;
+  pin_get(e, &n_groups32, gpos + n, 4);
+  pin_sync(e);
+  ms += E.ms(0, 1);
+  const uint64_t G = n_groups32;
+  if (!G || G > n) throw BjxError(BJX_ERR_DEVICE, "internal: groups runs disagree with the keys");
+  if (list && G > room) throw BjxError(BJX_ERR_CAPACITY, who + ": more groups than the node merges");
+  bjx_groups::Rec *recs = tmp.get<bjx_groups::Rec>(G);
+  if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, who + ": no device memory for the groups");
+  HIP_OK(hipEventRecord(E.ev[0], st));
+  HIP_OK(hipMemsetAsync(recs, 0, G * sizeof(bjx_groups::Rec), st));
+  hipLaunchKernelGGL(k_grp_runs, dim3((unsigned)((n + kGrpTile - 1) / kGrpTile)), dim3(kBlock), 0, st, n, s_lo, s_hi, s_id, head, gpos,
+                     n_ips, d_acc, G, recs);
+  HIP_OK(hipGetLastError());
+  if (list) {
+    HIP_OK(hipEventRecord(E.ev[1], st));
+    list->resize(G);
+    HIP_OK(hipMemcpyAsync(list->data(), recs, G * sizeof(bjx_groups::Rec), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    ms += E.ms(0, 1);
+    return done();
+  }
+
+  // 4. min_ips (a stable compaction), the order (a stable sort), the first rows
+  bjx_groups::Rec *d_rows = tmp.get<bjx_groups::Rec>(std::min<uint64_t>(g->limit, G));
+  uint32_t *ok = tmp.get<uint32_t>(G + 1), *pos = tmp.get<uint32_t>(G + 1);
+  if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, who + ": no device memory for the rows");
+  hipLaunchKernelGGL(k_grp_ok, dim3(grid_for(G + 1)), dim3(kBlock), 0, st, G, recs, g->min_ips, ok);
+  HIP_OK(hipGetLastError());
+  cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, ok, pos, (int)(G + 1), st); });
+  HIP_OK(hipEventRecord(E.ev[1], st));
+  uint32_t n_min32 = 0;
+  pin_get(e, &n_min32, pos + G, 4);
+  pin_sync(e);
+  ms += E.ms(0, 1);
+  const uint64_t n_min = n_min32;
+  if (n_min > G) throw BjxError(BJX_ERR_DEVICE, "internal: groups compaction disagrees with the runs");
+  out->n_groups = G;
+  out->n_groups_min = n_min;
+  const uint64_t n_rows = std::min<uint64_t>(g->limit, n_min);
+  if (!n_rows) return done();
+  uint64_t *pr0 = tmp.get<uint64_t>(n_min), *pr1 = tmp.get<uint64_t>(n_min);
+  uint32_t *gi0 = tmp.get<uint32_t>(n_min), *gi1 = tmp.get<uint32_t>(n_min);
+  if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, who + ": no device memory for the order");
+  const uint64_t top = g->order == BJX_GROUPS_BY_IPS ? n : matched;  // no group has more IPs / states
+  const int bits = g->order == BJX_GROUPS_BY_HITS ? 64 : std::max(1, bit_width(top));
+  HIP_OK(hipEventRecord(E.ev[0], st));
+  hipLaunchKernelGGL(k_grp_prim, dim3(grid_for(G)), dim3(kBlock), 0, st, G, recs, ok, pos, n_min, g->order, top, pr0, gi0);
+  HIP_OK(hipGetLastError());
+  cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, pr0, pr1, gi0, gi1, (int)n_min, 0, bits, st); });
+  hipLaunchKernelGGL(k_grp_rows, dim3(grid_for(n_rows)), dim3(kBlock), 0, st, n_rows, gi1, G, recs, d_rows);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord(E.ev[1], st));
+  std::vector<bjx_groups::Rec> h_rows(n_rows);
+  HIP_OK(hipMemcpyAsync(h_rows.data(), d_rows, n_rows * sizeof(bjx_groups::Rec), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  ms += E.ms(0, 1);
+  e->grp_rows.reserve(n_rows);
+  for (const bjx_groups::Rec &r : h_rows) e->grp_rows.push_back(bjx_groups::row_of(r, *g));
+  out->n_rows = n_rows;
+  out->rows = e->grp_rows.data();
+  return done();
+}
+
+}  // namespace
+
+// test hook (include/banjax_gpu_debug.h): the sorted keys one block of k_grp_runs reduces
+extern "C" uint32_t bjx_debug_groups_tile(void) { return kGrpTile; }
+
+extern "C" int bjx_state_query_groups(bjx_engine *e, const bjx_state_filter *f, const bjx_group_spec *g, bjx_state_groups *out) {
+  if (!e || !f || !g || !out) return BJX_ERR_ARG;
+  return guarded(e, [&]() -> int { return groups_locked(e, f, g, out, 0, nullptr, nullptr); });
+}
+
+int bjx_groups_list(bjx_engine *e, const bjx_state_filter *f, const bjx_group_spec *g, uint64_t room,
+                    std::vector<bjx_groups::Rec> *list, bjx_groups::Counts *counts) {
+  if (!e || !f || !g || !list || !counts) return BJX_ERR_ARG;
+  return guarded(e, [&]() -> int { return groups_locked(e, f, g, nullptr, room, list, counts); });
+}

@@ -496,6 +496,43 @@ class Engine:
         self._check(getattr(_lib.lib(), self._trim)(self._h, C.byref(bud), C.byref(st)), "state_trim")
         return {k: getattr(st, k) for k, _ in _lib.TrimStats._fields_}
 
+    _groups = "bjx_state_query_groups"
+
+    def state_query_groups(self, v4_bits: int = 24, v6_bits: int = 64, order=_lib.GROUPS_BY_IPS, limit: int = 100,
+                           min_ips: int = 0, ip=None, name=None, min_hits: int = INT64_MIN,
+                           min_start_ns: int = INT64_MIN, max_start_ns: int = INT64_MAX) -> dict:
+        """The networks that hold the most counting IPs: the held IPs with a
+        state that passes the filter (state_query's ip, name, min_hits,
+        min_start_ns, max_start_ns), grouped by their address masked to
+        v4_bits / v6_bits (bjx_state_query_groups; banjax_amd/state_groups.py
+        documents the grouping and the order and is its model).  order:
+        _lib.GROUPS_BY_IPS, _BY_STATES or _BY_HITS (or "ips" / "states" /
+        "hits"); rows only for groups of at least min_ips IPs; limit 0: the
+        counts only.  Returns {"n_matched", "n_ips_matched", "n_ips_unparsed",
+        "n_states_unparsed", "n_groups", "n_groups_min", "rows":
+        [state_groups.GroupRow], "device_ms"}.  A row's .net ("170.85.195.0/24",
+        "2001:db8:85a3:c55a::/64") is an entry state_query(nets=[...]) and
+        state_remove(nets=[...]) take as it is.  The engine is unchanged."""
+        from .state_groups import GroupRow, net_text
+        order = {"ips": _lib.GROUPS_BY_IPS, "states": _lib.GROUPS_BY_STATES, "hits": _lib.GROUPS_BY_HITS}.get(order, order)
+        ipb = None if ip is None else _lib.b(ip)
+        nb = None if name is None else _lib.b(name)
+        f = _lib.StateFilter(_lib.Str(ipb, len(ipb or b"")), _lib.Str(nb, len(nb or b"")), min_hits, min_start_ns,
+                             max_start_ns, _lib.QUERY_BY_HITS, 0)
+        g = _lib.GroupSpec(v4_bits, v6_bits, order, limit, min_ips)
+        out = _lib.StateGroups()
+        self._check(getattr(_lib.lib(), self._groups)(self._h, C.byref(f), C.byref(g), C.byref(out)), "state_query_groups")
+        rows = []
+        for k in range(out.n_rows):
+            r = out.rows[k]
+            addr = bytes(r.addr)
+            rows.append(GroupRow(net_text(r.family, r.bits, addr), r.family, r.bits, addr, r.n_ips, r.n_states, r.hits_sum,
+                                 r.newest_start_ns))
+        ans = {k: getattr(out, k) for k in ("n_matched", "n_ips_matched", "n_ips_unparsed", "n_states_unparsed", "n_groups",
+                                            "n_groups_min", "device_ms")}
+        ans["rows"] = rows
+        return ans
+
     def debug_set_trim_grid(self, max_blocks: int):
         """Test hook: the block cap of state_trim's counting passes (0 = default)."""
         self._check(_lib.lib().bjx_debug_set_trim_grid(self._h, max_blocks), "debug_set_trim_grid")
@@ -671,6 +708,9 @@ class Node:
 
     _trim = "bjx_node_state_trim"
     state_trim = Engine.state_trim  # the budget per engine, one cutoff for the node (the engines' largest); stats summed
+
+    _groups = "bjx_node_state_query_groups"
+    state_query_groups = Engine.state_query_groups  # the shards' complete group lists merged by key, then min_ips, order, limit
 
     _rule_stats = "bjx_node_"
     rule_stats = Engine.rule_stats  # the engines' arrays summed; engine(k).rule_stats() has engine k's own

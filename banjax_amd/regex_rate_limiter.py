@@ -586,6 +586,20 @@ class RegexRateLimiter:
             return self.engine.state_trim(max_states=max_states, max_ips=max_ips,
                                           floor_cutoff_ns=expire_cutoff_ns(now_ns, self._snap.config), dry_run=dry_run)
 
+    def top_networks(self, v4_bits: int = 24, v6_bits: int = 64, limit: int = 20, min_ips: int = 2, order="ips",
+                     now_ns: Optional[int] = None, **filt) -> dict:
+        """The networks that hold the most counting IPs right now
+        (Engine.state_query_groups): what to look at during a flood of distinct
+        source addresses.  With now_ns only the states expire_states(now_ns)
+        would keep are counted.  filt: state_query_groups' name, min_hits and
+        start window.  A row's .net goes as it is into an allow list or into
+        engine.state_remove(nets=[...])."""
+        with self._mu:
+            if now_ns is not None:
+                filt.setdefault("min_start_ns", expire_cutoff_ns(now_ns, self._snap.config))
+            return self.engine.state_query_groups(v4_bits=v4_bits, v6_bits=v6_bits, order=order, limit=limit, min_ips=min_ips,
+                                                  **filt)
+
     def export_states(self, now_ns: Optional[int] = None) -> bytes:
         """The rate-limit state as a snapshot blob (Engine.state_export) for the
         host to write out on shutdown.  With now_ns only what expire_states(now_ns)

@@ -611,6 +611,79 @@ typedef struct bjx_trim_stats {    /* 104 B */
   double device_ms;                  /* select + mark/scan + rebuild, copies excluded */
 } bjx_trim_stats;
 int bjx_state_trim(bjx_engine *e, const bjx_trim_budget *b, bjx_trim_stats *out);
+/* ---- Groups: the networks that hold the most counting IPs.  The nets calls
+   act on a network once somebody names it; this call finds it.  During a flood
+   of distinct source addresses "which /24s (or IPv6 /64s) hold the most IPs
+   right now" becomes an allow entry, a ban or a bjx_state_remove_nets call,
+   and the distribution lives in HBM.
+
+   Selection: a state is selected when it has valid != 0 and passes the five
+   conditions of *f exactly as bjx_state_query reads them (ip, name, min_hits,
+   min_start_ns, max_start_ns).  f->order and f->limit change nothing in the
+   answer (a filter bjx_state_query refuses is still refused); f->ip is
+   honoured: the groups of that one IP's selected states.  An IP is selected
+   when at least one of its states is.
+
+   Group of an IP: its stored bytes are parsed as net.ParseIP parses them.
+   Text that does not parse belongs to no group and is counted in
+   n_ips_unparsed / n_states_unparsed.  A v4-mapped address (dotted-quad text
+   or ::ffff:a.b.c.d text) is IPv4 and is masked to v4_bits; every other
+   address is IPv6 and is masked to v6_bits.  The group is (family, masked
+   address).  This is the membership rule of the nets calls: for every row,
+   bjx_state_query_nets with the same *f, limit 0 and the single entry
+   addr/bits reports n_matched == n_states and net_ips[0] == n_ips.
+
+   Rows: the groups with n_ips >= min_ips, ordered by the primary key
+   descending -- n_ips, n_states or hits_sum (as signed int64) -- then family 4
+   before family 6, then addr bytewise ascending; the first `limit` of them.
+   The order is total and a function of the logical state alone: slot layout,
+   table sizes and the debug hash mask do not show.  hits_sum wraps as Go's
+   int addition does.  Over all groups, the n_ips add up to n_ips_matched -
+   n_ips_unparsed and the n_states to n_matched - n_states_unparsed.
+
+   Not errors (zero rows, zero counts): an engine without state, a name the
+   engine never interned, an empty start window.  BJX_ERR_ARG, with the engine
+   unchanged: a NULL handle, f, g or out; v4_bits > 32; v6_bits > 128; an
+   unknown order; limit > BJX_GROUPS_MAX_ROWS; what bjx_state_query refuses in
+   *f, and f->ip or f->name with len > 0 and a NULL ptr; a call between
+   bjx_match_batch and its bjx_finish_batch* (the node call waits for the node
+   batch instead).  BJX_ERR_NOMEM: a failed allocation.  The engine is
+   unchanged in every case: the tables are only read.  rows is engine-owned and
+   valid until the next groups query on the handle.  Takes the engine lock
+   like the other bjx_state_* calls.
+
+   Temporary device memory: proportional to the held IPs, 32 bytes per held IP
+   (a state count, a hits sum and a newest start each) and at most about 170
+   per selected IP (sort keys, their permutation, the group records); no
+   per-state temporary -- the state table is read in place, once. */
+enum bjx_group_order { BJX_GROUPS_BY_IPS = 0, BJX_GROUPS_BY_STATES = 1, BJX_GROUPS_BY_HITS = 2 };
+#define BJX_GROUPS_MAX_ROWS 65536
+typedef struct bjx_group_spec {     /* 24 B */
+  uint32_t v4_bits;   /* 0..32:  prefix length IPv4 addresses are grouped by */
+  uint32_t v6_bits;   /* 0..128: the same for IPv6 */
+  uint32_t order;     /* enum bjx_group_order */
+  uint32_t limit;     /* rows wanted, 0..BJX_GROUPS_MAX_ROWS; 0: counts only */
+  uint64_t min_ips;   /* rows only for groups with n_ips >= min_ips (0 and 1: every group) */
+} bjx_group_spec;
+typedef struct bjx_group_row {      /* 56 B */
+  uint8_t addr[16];   /* the masked network; IPv4 in addr[0..4), the rest 0 */
+  uint32_t family;    /* 4 or 6 */
+  uint32_t bits;      /* v4_bits or v6_bits */
+  uint64_t n_ips;     /* distinct held IPs of the group with a selected state */
+  uint64_t n_states;  /* selected states of those IPs */
+  int64_t hits_sum;   /* sum of their hits, wrapping as Go int addition */
+  int64_t newest_start_ns; /* largest interval_start_ns among them */
+} bjx_group_row;
+typedef struct bjx_state_groups {   /* 72 B */
+  uint64_t n_matched, n_ips_matched;          /* exactly bjx_state_query's for the same *f */
+  uint64_t n_ips_unparsed, n_states_unparsed; /* selected, but the IP text is no address: in no group */
+  uint64_t n_groups;      /* distinct groups */
+  uint64_t n_groups_min;  /* those with n_ips >= min_ips */
+  uint64_t n_rows;        /* min(limit, n_groups_min) */
+  const bjx_group_row *rows;  /* engine-owned (node-owned), valid until the next groups query on the handle */
+  double device_ms;       /* HIP events, copies excluded */
+} bjx_state_groups;
+int bjx_state_query_groups(bjx_engine *e, const bjx_state_filter *f, const bjx_group_spec *g, bjx_state_groups *out);
 /* RegexRateLimitStates.String(): "ip:\n\trule:\n\t\t{hits start}\n" blocks, IPs in
    first-seen order.  Returns the full length (writes at most cap bytes). */
 size_t bjx_state_dump(bjx_engine *e, char *out, size_t cap);
@@ -862,6 +935,19 @@ int bjx_node_state_remove_nets(bjx_node *n, const bjx_state_filter *f, const bjx
    first failure is returned and the call is idempotent, so the caller repeats
    it, as with bjx_node_state_remove.  out may be NULL. */
 int bjx_node_state_trim(bjx_node *n, const bjx_trim_budget *b, bjx_trim_stats *out);
+/* bjx_state_query_groups over the node.  A group spans engines (the owner of
+   an IP is a hash of its bytes), so the shards' top rows do not determine the
+   node's: every engine builds its complete group list in key order, the host
+   merges the lists by key (counts and hits summed, the newest start the
+   largest) and only then applies min_ips, the order and the limit -- a group
+   below min_ips on every shard can still reach it in total.  The answer equals
+   one engine over the union of the state.  n_matched, n_ips_matched and the
+   unparsed counts are summed, device_ms is the slowest shard's.  When the
+   shards' lists together hold more than 2^24 groups the call returns
+   BJX_ERR_CAPACITY (use shorter prefixes or a narrower filter).  rows is
+   node-owned until the next groups query on the node.  Waits for the node
+   batch, as bjx_node_state_expire does. */
+int bjx_node_state_query_groups(bjx_node *n, const bjx_state_filter *f, const bjx_group_spec *g, bjx_state_groups *out);
 /* bjx_batch_rule_stats / bjx_rule_stats_total / bjx_rule_stats_reset over the
    node: the engines' arrays summed (engine k counted chunk k's lines),
    n_lines summed, device_ms the slowest engine's (totals: those summed). */

@@ -74,6 +74,9 @@ int bjx_debug_set_bucket_bits(bjx_engine *e, uint32_t bits);
    over the per-IP newest starts) launch at most max_blocks blocks (0 = the
    default cap), so that their grid-stride loops wrap on small inputs. */
 int bjx_debug_set_trim_grid(bjx_engine *e, uint32_t max_blocks);
+/* The number of sorted keys one block of bjx_state_query_groups' run reduction
+   (k_grp_runs) handles: the tests place group sizes and boundaries around it. */
+uint32_t bjx_debug_groups_tile(void);
 /* Test hook: the state-table slot index each of n (IP, rule name) states
    occupies, found as bjx_state_get finds it (hash, probe chain, IP bytes,
    then the state's key), in one launch for the whole list; -1 where there is
