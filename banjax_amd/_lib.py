@@ -309,6 +309,13 @@ def lib():
     L.bjx_debug_set_slot_cache.argtypes = [vp, C.c_int]
     L.bjx_debug_set_bucket_bits.restype = C.c_int
     L.bjx_debug_set_bucket_bits.argtypes = [vp, C.c_uint32]
+    L.bjx_debug_set_rec8_max_events.restype = C.c_int
+    L.bjx_debug_set_rec8_max_events.argtypes = [vp, C.c_uint64]
+    L.bjx_debug_event_record.restype = C.c_int
+    L.bjx_debug_event_record.argtypes = [C.c_uint32, C.c_int64, C.c_uint32, C.c_int, C.c_uint32, C.c_int64,
+                                         C.POINTER(C.c_int64)]
+    L.bjx_debug_event_record_bits.restype = C.c_int
+    L.bjx_debug_event_record_bits.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
     L.bjx_debug_state_slots.restype = C.c_int
     L.bjx_debug_state_slots.argtypes = [vp, vp, vp, C.POINTER(Str), sz, vp, sz, vp]
     L.bjx_debug_set_ip_hash_mask.restype = C.c_int

@@ -3430,8 +3430,9 @@ __global__ void k_ip_collide(EvSrc E, State S, uint32_t epoch, uint32_t *__restr
 
 // event k -> state slot and its sort record.  seenIp is false only for the
 // first event of an IP created in this batch.
-// A record whose timestamp the 12-B form cannot hold raises flag 8 (the host
-// claims the batch again in the 16-B form).
+// An event that the record form cannot hold (R::fits: a timestamp outside
+// the form's span, for the 8-B form also one that is not a $msec value) raises
+// flag 8: the host claims the batch again in the next wider form.
 template <typename R>
 __device__ __forceinline__ bool st_claim_event(const EvSrc &E, uint64_t n_ev, uint64_t k, const uint32_t *__restrict__ ev_el,
                                                const uint32_t *__restrict__ ev_rule, const uint32_t *__restrict__ el_slot,
@@ -4236,12 +4237,12 @@ __global__ void k_check_masks(uint64_t n_lines, Lines L, uint32_t mask_words, un
   if ((uint32_t)(L.counts[j] >> 32) != pc && atomicAdd(&chk[0], 1ull) == 0) chk[1] = j;
 }
 
-// BJX_CHECK: cnt[idx[t * step]] += 1 for t < n (idx < cap, else chk[0]++)
-__global__ void k_check_count(uint64_t n, const uint32_t *__restrict__ idx, uint32_t step, uint64_t cap,
+// BJX_CHECK: cnt[idx[t * step] & mask] += 1 for t < n (idx < cap, else chk[0]++)
+__global__ void k_check_count(uint64_t n, const uint32_t *__restrict__ idx, uint32_t step, uint32_t mask, uint64_t cap,
                               uint32_t *__restrict__ cnt, unsigned long long *__restrict__ chk) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
-  const uint32_t v = idx[t * step];
+  const uint32_t v = idx[t * step] & mask;
   if (v < cap) atomicAdd(&cnt[v], 1u);
   else atomicAdd(&chk[0], 1ull);
 }
@@ -4252,18 +4253,18 @@ __global__ void k_check_most(uint64_t n, const uint32_t *__restrict__ cnt, uint3
 }
 
 // sorted outcomes -> event order (evw: the sorted records' event index words,
-// `stride` words apart: either record form)
-__global__ void k_unsort(uint64_t n, const uint32_t *__restrict__ evw, uint32_t stride, const uint8_t *__restrict__ in,
-                         uint8_t *__restrict__ out) {
+// `stride` words apart, the index in the bits of `mask`: any record form)
+__global__ void k_unsort(uint64_t n, const uint32_t *__restrict__ evw, uint32_t stride, uint32_t mask,
+                         const uint8_t *__restrict__ in, uint8_t *__restrict__ out) {
   const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (u < n) out[evw[u * stride]] = in[u];
+  if (u < n) out[evw[u * stride] & mask] = in[u];
 }
 
 // event index of each trip found in sorted order
 __global__ void k_trip_events(uint64_t n, const uint32_t *__restrict__ pos, const uint32_t *__restrict__ evw, uint32_t stride,
-                              uint32_t *__restrict__ ev) {
+                              uint32_t mask, uint32_t *__restrict__ ev) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) ev[t] = evw[(uint64_t)pos[t] * stride];
+  if (t < n) ev[t] = evw[(uint64_t)pos[t] * stride] & mask;
 }
 
 struct TripBit {
@@ -5179,9 +5180,14 @@ struct bjx_engine {
   DevBuf<uint64_t> res_seq;
   bool res_written = false;  // the last match phase wrote the RuleResult arrays
   DevBuf<uint32_t> res_rule, ev_el, ev_rule, ev_res, ev_st, ev_st2, ev_idx, ev_idx2, el_slot, coll, trip_idx;
-  DevBuf<EvRec> ev_rec, ev_rec2;  // EvRec12 records when rec12 (the last rate-limit stage's form), from rec_base
-  bool rec12 = false;
+  // sized for the widest form; EvRec8 / EvRec12 records when rec_bytes (the last rate-limit
+  // stage's record size: 8, 12 or 16) says so, from rec_base (ms for the 8-B form)
+  DevBuf<EvRec> ev_rec, ev_rec2;
+  uint32_t rec_bytes = 16;
   int64_t rec_base = 0;
+  // after a batch that fell back to a wider form, rec_hold batches start at that form (rec_floor)
+  uint32_t rec_floor = 8, rec_hold = 0;
+  uint64_t dbg_rec8_max_ev = 0;  // bjx_debug_set_rec8_max_events: 0 = the event index field's 2^28
   DevBuf<uint32_t> el_id;
   DevBuf<uint32_t> blk_n;   // k_ip_firsts: first lines per block, then their exclusive scan
   DevBuf<uint64_t> blk_b;   // ... and their IP bytes
@@ -6639,9 +6645,11 @@ void bind_ruleset(bjx_engine *e, const bjx_ruleset *rs, const uint8_t *sample, s
 // the sorted records' event index words and their stride, in the form the
 // last rate-limit stage used
 static const uint32_t *ev_words(const bjx_engine *e) {
-  return reinterpret_cast<const uint32_t *>(e->ev_rec2.p) + (e->rec12 ? 2 : 3);
+  return reinterpret_cast<const uint32_t *>(e->ev_rec2.p) + (e->rec_bytes == 8 ? 0 : e->rec_bytes == 12 ? 2 : 3);
 }
-static uint32_t rec_stride(const bjx_engine *e) { return e->rec12 ? 3u : 4u; }
+static uint32_t rec_stride(const bjx_engine *e) { return e->rec_bytes / 4; }
+// the 8-B form's index shares its word with the first-event bit and the rule's low bits
+static uint32_t ev_mask(const bjx_engine *e) { return e->rec_bytes == 8 ? EvRec8::kEvMask : 0xFFFFFFFFu; }
 
 // Small device -> host reads: pin_get queues a copy into the engine's pinned
 // ring (the value lands in dst at the next pin_sync, which waits for the
@@ -6888,6 +6896,29 @@ static uint64_t rl_apply_sorted(bjx_engine *e, const Bind &B, uint64_t n_ev, con
 // Phases 5 (IP + state slots), 6 (sort), 7 (automaton).
 // the event sort (state slot keys, records as values) and the Apply kernels,
 // for either record form
+// The event sort's onesweep configuration.  For 4-B keys with values of 5 to 8 bytes rocprim's
+// tuned choice on this GPU is 1024 threads x 8 items, with which the 8-B records sort slower than
+// the 12-B ones do with the 1024 x 6 it picks for those (sort + apply 8.7 against 8.5 ms per cfg3
+// batch).  1024 x 10 (120 KB of LDS, one block per CU as before) measured best of the five
+// shapes tried: 7.5 ms (profiles/event_rec8).  -DBJX_SORT8_BLOCK=0 gives rocprim's choice back.
+#ifndef BJX_SORT8_BLOCK
+#define BJX_SORT8_BLOCK 1024
+#define BJX_SORT8_ITEMS 10
+#endif
+template <typename Rec>
+struct EvSortConfig {
+  using type = rocprim::default_config;
+};
+#if BJX_SORT8_BLOCK
+template <>
+struct EvSortConfig<EvRec8> {
+  using kernel = rocprim::kernel_config<BJX_SORT8_BLOCK, BJX_SORT8_ITEMS>;
+  using type = rocprim::radix_sort_config<
+      rocprim::default_config, rocprim::default_config,
+      rocprim::radix_sort_onesweep_config<kernel, kernel, 8, rocprim::block_radix_rank_algorithm::match>>;
+};
+#endif
+
 template <typename Rec>
 static void rl_sort_apply(bjx_engine *e, const Bind &B, const EvSrc &E, uint64_t n_ev, const uint32_t *ev_el,
                           const uint32_t *ev_rule, int64_t base) {
@@ -6934,7 +6965,8 @@ static void rl_sort_apply(bjx_engine *e, const Bind &B, const EvSrc &E, uint64_t
     Rec *vi = reinterpret_cast<Rec *>(e->ev_rec.p), *vo = reinterpret_cast<Rec *>(e->ev_rec2.p);
     const int lo = two ? L : 0;
     cub_call(e, [&](void *tmp, size_t &bytes) {
-      return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ki, ko, vi, vo, (int)n_ev, lo, bits, st);
+      return rocprim::radix_sort_pairs<typename EvSortConfig<Rec>::type>(tmp, bytes, ki, ko, vi, vo, (unsigned)n_ev, (unsigned)lo,
+                                                                        (unsigned)bits, st);
     });
   }
   uint32_t *wcnt = nullptr;
@@ -7020,7 +7052,7 @@ static void rl_sort_apply(bjx_engine *e, const Bind &B, const EvSrc &E, uint64_t
     HIP_OK(hipMemsetAsync(e->chk.p, 0, 128, st));
     uint32_t *pc = wcnt + n_ev;
     hipLaunchKernelGGL(k_check_count, dim3(grid_for(n_ev)), dim3(kBlock), 0, st, n_ev,
-                       ev_words(e), rec_stride(e), n_ev, pc, e->chk.p + 14);
+                       ev_words(e), rec_stride(e), ev_mask(e), n_ev, pc, e->chk.p + 14);
     hipLaunchKernelGGL(k_check_rl, dim3(grid_for(std::max<uint64_t>(E.n, n_ev))), dim3(kBlock), 0, st, E, n_ev, ev_el, ev_rule,
                        e->el_slot.p, e->el_id.p, B.rules, e->S, e->ev_st.p, e->ev_out_s.p, wcnt, pc, e->chk.p);
     HIP_OK(hipGetLastError());
@@ -7042,16 +7074,52 @@ static void rl_sort_apply(bjx_engine *e, const Bind &B, const EvSrc &E, uint64_t
   }
 }
 
-// rec_base (kNoRecBase: none): the events' timestamps are expected within
-// 2^43 ns of it either way, so the sort carries 12-B records (EvRec12).
+// rec_base (kNoRecBase: none): the batch's clock.  The events' timestamps are
+// expected within 2^23 ms of it either way and to be $msec values, so the sort
+// carries 8-B records (EvRec8); within 2^43 ns, 12-B records (EvRec12).
 constexpr int64_t kNoRecBase = INT64_MIN;
+template <typename Rec>
+static void launch_st_claim(bjx_engine *e, const Bind &B, const EvSrc &E, uint64_t n_ev, const uint32_t *ev_el,
+                            const uint32_t *ev_rule, int64_t base, uint64_t shard_budget) {
+  hipLaunchKernelGGL(k_st_claim<Rec>, dim3(grid_for(n_ev)), dim3(kBlock), 0, e->stream, E, n_ev, ev_el, ev_rule, e->el_slot.p,
+                     e->el_id.p, B.rules, e->S, e->ev_st.p, reinterpret_cast<Rec *>(e->ev_rec.p), base, shard_budget);
+}
+// the claim pass writing records of `form` bytes; the records' base for the batch clock `now`
+static int64_t st_claim_form(bjx_engine *e, uint32_t form, const Bind &B, const EvSrc &E, uint64_t n_ev, const uint32_t *ev_el,
+                             const uint32_t *ev_rule, int64_t now, uint64_t shard_budget) {
+  int64_t base = 0;
+  if (form == 8) {
+    base = now / 1000000 - (EvRec8::kSpanMs >> 1);
+    launch_st_claim<EvRec8>(e, B, E, n_ev, ev_el, ev_rule, base, shard_budget);
+  } else if (form == 12) {
+    base = (int64_t)((uint64_t)now - (EvRec12::kSpan >> 1));
+    launch_st_claim<EvRec12>(e, B, E, n_ev, ev_el, ev_rule, base, shard_budget);
+  } else {
+    launch_st_claim<EvRec>(e, B, E, n_ev, ev_el, ev_rule, base, shard_budget);
+  }
+  return base;
+}
 static void rate_limit_stage(bjx_engine *e, const Bind &B, const EvSrc &E, uint64_t n_el, uint64_t el_bytes, uint64_t n_ev,
                              const uint32_t *ev_el, const uint32_t *ev_rule, int64_t rec_base) {
   hipStream_t st = e->stream;
-  const bool force16 = getenv("BJX_REC16") != nullptr;  // test hook: the 16-B records throughout
-  bool use12 = rec_base != kNoRecBase && B.n_rules < (1u << EvRec12::kRuleBits) && !force16;
-  if (use12) rec_base = (int64_t)((uint64_t)rec_base - (EvRec12::kSpan >> 1));
-  else rec_base = 0;
+  // test hooks, read per batch: BJX_REC16 the 16-B records throughout, BJX_REC12 nothing narrower than 12 B
+  const bool force16 = getenv("BJX_REC16") != nullptr, cap12 = getenv("BJX_REC12") != nullptr;
+  const int64_t now = rec_base;
+  const bool ok12 = now != kNoRecBase && B.n_rules < (1u << EvRec12::kRuleBits) && !force16;
+  const uint64_t max_ev8 = e->dbg_rec8_max_ev ? e->dbg_rec8_max_ev : (1ull << EvRec8::kEvBits);
+  const bool ok8 = ok12 && !cap12 && B.n_rules <= (1u << EvRec8::kRuleBits) && n_ev <= max_ev8;
+  // a stream whose batches fall back (timestamps that are not $msec values, say) starts its next
+  // kRecHold batches at the form that worked, then tries the narrower one again, so it pays the
+  // wasted claim pass once in kRecHold + 1 batches (BJX_REC_HOLD: test hook, as BJX_SORT2_HOLD)
+  const char *rhold_env = getenv("BJX_REC_HOLD");
+  const uint32_t kRecHold = rhold_env ? (uint32_t)atoi(rhold_env) : 32u;
+  uint32_t floor_form = 8;
+  if (e->rec_hold) {
+    --e->rec_hold;
+    floor_form = e->rec_floor;
+  }
+  uint32_t form = ok8 && floor_form <= 8 ? 8u : ok12 && floor_form <= 12 ? 12u : 16u;
+  const uint32_t form0 = form;
   if (E.n >= 0x7FFFFFFFull || n_ev >= 0xFFFFFFFFull) throw BjxError(BJX_ERR_ARG, "batch too large (2^31 lines / 2^32 events)");
   if (!e->counters_fresh) read_counters(e);
   e->counters_fresh = false;
@@ -7138,30 +7206,28 @@ static void rate_limit_stage(bjx_engine *e, const Bind &B, const EvSrc &E, uint6
       uint64_t budget = e->st_cap * 3 / 4 - n_st;
       const bool forced = e->dbg_budget && attempt == 0 && e->dbg_budget < budget;  // test hook
       if (forced) budget = e->dbg_budget;
-      if (use12)
-        hipLaunchKernelGGL(k_st_claim<EvRec12>, dim3(grid_for(n_ev)), dim3(kBlock), 0, st, E, n_ev, ev_el, ev_rule,
-                           e->el_slot.p, e->el_id.p, B.rules, e->S, e->ev_st.p, reinterpret_cast<EvRec12 *>(e->ev_rec.p),
-                           rec_base, budget / kClaimShards);
-      else
-        hipLaunchKernelGGL(k_st_claim<EvRec>, dim3(grid_for(n_ev)), dim3(kBlock), 0, st, E, n_ev, ev_el, ev_rule,
-                           e->el_slot.p, e->el_id.p, B.rules, e->S, e->ev_st.p, e->ev_rec.p, rec_base, budget / kClaimShards);
+      rec_base = st_claim_form(e, form, B, E, n_ev, ev_el, ev_rule, now, budget / kClaimShards);
       // the shard counts folded into the table count right away (an overflow
       // below rolls the claims back and recounts), read with the flags
       hipLaunchKernelGGL(k_fold_claims, dim3(1), dim3(kClaimShards), 0, st, e->S);
       HIP_OK(hipGetLastError());
-      uint64_t ovf[2] = {0, 0};  // state table overflow, a timestamp outside the 12-B records' span
+      uint64_t ovf[2] = {0, 0};  // state table overflow, an event the record form cannot hold
       pin_get(e, ovf, e->S.counters + 7, 16);
       pin_get(e, e->host_counters, e->S.counters, 24);
       pin_sync(e);
       if (!ovf[0]) {
-        if (use12 && ovf[1]) {
+        while (form != 16 && ovf[1]) {
           // the same claims again (every key is in the table now, so nothing
-          // is claimed twice), writing 16-B records
-          use12 = false;
-          rec_base = 0;
-          hipLaunchKernelGGL(k_st_claim<EvRec>, dim3(grid_for(n_ev)), dim3(kBlock), 0, st, E, n_ev, ev_el, ev_rule,
-                             e->el_slot.p, e->el_id.p, B.rules, e->S, e->ev_st.p, e->ev_rec.p, rec_base, budget / kClaimShards);
+          // is claimed twice), writing the next wider records
+          form = form == 8 && ok12 ? 12u : 16u;
+          HIP_OK(hipMemsetAsync(e->S.counters + 8, 0, 8, st));
+          rec_base = st_claim_form(e, form, B, E, n_ev, ev_el, ev_rule, now, budget / kClaimShards);
           HIP_OK(hipGetLastError());
+          ovf[1] = 0;
+          if (form != 16) {
+            pin_get(e, &ovf[1], e->S.counters + 8, 8);
+            pin_sync(e);
+          }
         }
         break;
       }
@@ -7178,9 +7244,14 @@ static void rate_limit_stage(bjx_engine *e, const Bind &B, const EvSrc &E, uint6
   mark(e, 6);  // host_counters: read with the last claim pass's flags
   e->last_new_ips = e->host_counters[0] - ips0;
   e->last_new_states = e->host_counters[2] - st0;
-  e->rec12 = use12;
+  if (form != form0) {
+    e->rec_floor = form;
+    e->rec_hold = kRecHold;
+  }
+  e->rec_bytes = form;
   e->rec_base = rec_base;
-  if (use12) rl_sort_apply<EvRec12>(e, B, E, n_ev, ev_el, ev_rule, rec_base);
+  if (form == 8) rl_sort_apply<EvRec8>(e, B, E, n_ev, ev_el, ev_rule, rec_base);
+  else if (form == 12) rl_sort_apply<EvRec12>(e, B, E, n_ev, ev_el, ev_rule, rec_base);
   else rl_sort_apply<EvRec>(e, B, E, n_ev, ev_el, ev_rule, rec_base);
 }
 
@@ -7868,7 +7939,7 @@ static uint64_t trip_events(bjx_engine *e, uint64_t n_ev, FinishFrom from, uint6
   e->trip_ev.ensure(n_trips); e->trip_ev2.ensure(n_trips);
   if (from == kFinSorted)
     hipLaunchKernelGGL(k_trip_events, dim3(grid_for(n_trips)), dim3(kBlock), 0, st, n_trips, e->trip_idx.p, ev_words(e),
-                       rec_stride(e), e->trip_ev.p);
+                       rec_stride(e), ev_mask(e), e->trip_ev.p);
   uint32_t *ki = from == kFinSorted ? e->trip_ev.p : e->trip_idx.p, *ko = e->trip_ev2.p;
   const int bits = std::max(1, bit_width(n_ev));
   cub_call(e, [&](void *tmp, size_t &bytes) {
@@ -7935,8 +8006,8 @@ static void finish_phase(bjx_engine *e, uint32_t flags, bjx_batch_result *out, F
     }
     if (flags & BJX_COPY_RESULTS) {
       if (from == kFinSorted)
-        hipLaunchKernelGGL(k_unsort, dim3(grid_for(n_ev)), dim3(kBlock), 0, st, n_ev, ev_words(e), rec_stride(e), e->ev_out_s.p,
-                           e->ev_out.p);
+        hipLaunchKernelGGL(k_unsort, dim3(grid_for(n_ev)), dim3(kBlock), 0, st, n_ev, ev_words(e), rec_stride(e), ev_mask(e),
+                           e->ev_out_s.p, e->ev_out.p);
       hipLaunchKernelGGL(k_scatter_rl, dim3(grid_for(n_ev)), dim3(kBlock), 0, st, n_ev, e->ev_res.p, e->ev_out.p, e->rl_out.p);
       HIP_OK(hipGetLastError());
       if (getenv("BJX_CHECK")) {  // every event names its own RuleResult (ev_res injective)
@@ -7944,7 +8015,7 @@ static void finish_phase(bjx_engine *e, uint32_t flags, bjx_batch_result *out, F
         e->chk.ensure(16);
         HIP_OK(hipMemsetAsync(e->chk_w.p, 0, (n_res + 1) * 4, st));
         HIP_OK(hipMemsetAsync(e->chk.p, 0, 32, st));
-        hipLaunchKernelGGL(k_check_count, dim3(grid_for(n_ev)), dim3(kBlock), 0, st, n_ev, e->ev_res.p, 1u, n_res, e->chk_w.p,
+        hipLaunchKernelGGL(k_check_count, dim3(grid_for(n_ev)), dim3(kBlock), 0, st, n_ev, e->ev_res.p, 1u, 0xFFFFFFFFu, n_res, e->chk_w.p,
                            e->chk.p);
         hipLaunchKernelGGL(k_check_most, dim3(grid_for(n_res)), dim3(kBlock), 0, st, n_res, e->chk_w.p, 1u, e->chk.p);
         HIP_OK(hipGetLastError());
@@ -8191,8 +8262,8 @@ static int apply_received(bjx_engine *e, const bjx_ruleset *rs, const bjx_event_
     e->exchange_ms = x;
   }
   if (d_out) {
-    hipLaunchKernelGGL(k_unsort, dim3(grid_for(n_ev)), dim3(kBlock), 0, st, n_ev, ev_words(e), rec_stride(e), e->ev_out_s.p,
-                       d_out);
+    hipLaunchKernelGGL(k_unsort, dim3(grid_for(n_ev)), dim3(kBlock), 0, st, n_ev, ev_words(e), rec_stride(e), ev_mask(e),
+                       e->ev_out_s.p, d_out);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(st));
   }
@@ -8433,6 +8504,41 @@ extern "C" int bjx_debug_set_bucket_bits(bjx_engine *e, uint32_t bits) {
   e->dbg_bucket_bits = bits;
   return BJX_OK;
 }
+template <typename Rec>
+static void debug_record(int64_t ts, uint32_t rule, bool first, uint32_t ev, int64_t base, uint32_t ev_word, uint32_t mask,
+                         int64_t *out) {
+  const Rec v = Rec::make(ts, rule, first, ev, base);
+  uint32_t w[4] = {0, 0, 0, 0};
+  memcpy(w, &v, sizeof v);
+  out[0] = Rec::fits(ts, base) ? 1 : 0;
+  out[1] = v.time(base);
+  out[2] = v.rule_id();
+  out[3] = v.seen() ? 1 : 0;
+  out[4] = w[ev_word] & mask;  // as k_unsort and k_trip_events read it
+}
+extern "C" int bjx_debug_event_record(uint32_t form, int64_t ts, uint32_t rule, int first, uint32_t ev, int64_t base,
+                                      int64_t *out) {
+  if (!out) return BJX_ERR_ARG;
+  if (form == 8) debug_record<EvRec8>(ts, rule, first != 0, ev, base, 0, EvRec8::kEvMask, out);
+  else if (form == 12) debug_record<EvRec12>(ts, rule, first != 0, ev, base, 2, 0xFFFFFFFFu, out);
+  else if (form == 16) debug_record<EvRec>(ts, rule, first != 0, ev, base, 3, 0xFFFFFFFFu, out);
+  else return BJX_ERR_ARG;
+  return BJX_OK;
+}
+extern "C" int bjx_debug_event_record_bits(uint32_t form, uint32_t *out) {
+  if (!out) return BJX_ERR_ARG;
+  if (form == 8) { out[0] = EvRec8::kMsBits; out[1] = EvRec8::kRuleBits; out[2] = EvRec8::kEvBits; }
+  else if (form == 12) { out[0] = 44; out[1] = EvRec12::kRuleBits; out[2] = 32; }
+  else if (form == 16) { out[0] = 64; out[1] = 31; out[2] = 32; }
+  else return BJX_ERR_ARG;
+  return BJX_OK;
+}
+extern "C" int bjx_debug_set_rec8_max_events(bjx_engine *e, uint64_t max_events) {
+  if (!e || max_events > (1ull << EvRec8::kEvBits)) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->dbg_rec8_max_ev = max_events;
+  return BJX_OK;
+}
 extern "C" int bjx_debug_set_trim_grid(bjx_engine *e, uint32_t max_blocks) {
   if (!e) return BJX_ERR_ARG;
   std::lock_guard<std::mutex> g(e->mu);
@@ -8541,11 +8647,11 @@ extern "C" size_t bjx_debug_scan_stats(bjx_engine *e, uint64_t *out, size_t cap)
   if (!e) return 0;
   std::lock_guard<std::mutex> g(e->mu);
   if (e->S.counters) read_counters(e);
-  const uint64_t v[12] = {e->scan_stats[0], e->scan_stats[1], e->scan_stats[2], e->scan_stats[3], e->scan_stats[4],
+  const uint64_t v[13] = {e->scan_stats[0], e->scan_stats[1], e->scan_stats[2], e->scan_stats[3], e->scan_stats[4],
                           e->ip_cap, e->host_counters[0], e->st_cap, e->host_counters[2], e->scan_stats[5],
-                          e->last_grouping, e->last_long_runs};
-  for (size_t k = 0; k < 12 && k < cap; ++k) out[k] = v[k];
-  return 12;
+                          e->last_grouping, e->last_long_runs, e->rec_bytes};
+  for (size_t k = 0; k < 13 && k < cap; ++k) out[k] = v[k];
+  return 13;
 }
 extern "C" int bjx_debug_rule_lead(const bjx_ruleset *rs, size_t i) {
   if (!rs || i >= rs->rules.size()) return BJX_ERR_ARG;

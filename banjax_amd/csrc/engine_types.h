@@ -314,7 +314,7 @@ struct State {
 // One rate-limit event as the sort carries it (16 B): line timestamp, rule
 // index | (first event of a new IP) << 31, event index (reference order).
 // The kernels of the rate-limit stage read it through time / rule_id / seen
-// (base: see EvRec12) and are instantiated for both record forms.
+// (base: see EvRec12, EvRec8) and are instantiated for every record form.
 struct EvRec {
   int64_t ts;
   uint32_t rule;
@@ -352,6 +352,64 @@ struct EvRec12 {
     v.lo = (uint32_t)d;
     v.hi = ((uint32_t)(d >> 32) & 0xFFFu) | (r << 12) | (first ? 0x80000000u : 0u);
     v.ev = ev;
+    return v;
+  }
+};
+
+// The 8-B form (tried first for a local batch): one 64-bit word of, from the
+// top, the timestamp as a millisecond offset from a base that is a whole
+// number of ms, the rule index, the first-event bit and the event index.  The
+// event sort moves 12 B per record per pass.  nginx's $msec timestamps are
+// texts S.mmm; the reference's int64(ParseFloat(text) * 1e9) of such a text is
+// ns_of_ms(1000 S + mmm) (not a multiple of 1 ms: at today's epoch it sits on
+// a 256-ns grid), so the ms count alone gives the line's ts back bit for bit.
+// The form does not rest on that: fits() holds only for a ts that equals
+// ns_of_ms of its own ms count, and a batch with any other event (or one
+// outside the span) is claimed again in the 12-B form.  base here is in ms.
+// RN(m / 1000) is computed without the divide's reciprocal iterations, which
+// sit on the apply kernels' serial per-run walks: with y = RN(1 / 1000) and
+// q0 = RN(m y), the remainder r = m - 1000 q0 is exact in one fma and
+// RN(q0 + r y) is the correctly rounded quotient (Markstein's theorem: y is the
+// correctly rounded reciprocal and q0 lies within one ulp of m / 1000).  Every
+// step is a correctly rounded IEEE operation on both sides, whatever the
+// build's flags; tests/test_event_records_cpu.py holds the result against the
+// oracle's parse, and fits() and time() share this one function, so an m for
+// which it gave another value than the line's ts would only cost the batch the
+// 12-B form.
+__host__ __device__ inline int64_t ns_of_ms(int64_t m) {
+  const double a = (double)m, y = 0.001;
+#ifdef __HIP_DEVICE_COMPILE__
+  const double q0 = __dmul_rn(a, y);
+  const double q = __fma_rn(__fma_rn(-1000.0, q0, a), y, q0);
+  return (int64_t)__dmul_rn(q, 1e9);
+#else
+  const double q0 = a * y;
+  const double q = __builtin_fma(__builtin_fma(-1000.0, q0, a), y, q0);
+  return (int64_t)(q * 1e9);
+#endif
+}
+struct EvRec8 {
+  uint64_t w;
+  static constexpr uint32_t kMsBits = 24, kRuleBits = 11, kFirstBits = 1, kEvBits = 28;
+  static_assert(kMsBits + kRuleBits + kFirstBits + kEvBits == 64, "one 64-bit word");
+  static constexpr uint32_t kRuleShift = kEvBits + kFirstBits, kMsShift = kRuleShift + kRuleBits;
+  static constexpr int64_t kSpanMs = 1ll << kMsBits;  // 4.7 h
+  static constexpr uint32_t kEvMask = (1u << kEvBits) - 1;  // the event index in the record's low word
+  __host__ __device__ int64_t time(int64_t base_ms) const { return ns_of_ms(base_ms + (int64_t)(w >> kMsShift)); }
+  __host__ __device__ uint32_t rule_id() const { return (uint32_t)(w >> kRuleShift) & ((1u << kRuleBits) - 1); }
+  __host__ __device__ bool seen() const { return ((w >> kEvBits) & 1) == 0; }
+  // the ms count of ts > 0 (below 2^44: an exact double)
+  __host__ __device__ static int64_t ms_of(int64_t ts) { return (int64_t)(((uint64_t)ts + 500000u) / 1000000u); }
+  __host__ __device__ static bool fits(int64_t ts, int64_t base_ms) {
+    if (ts <= 0) return false;
+    const int64_t m = ms_of(ts);
+    if ((uint64_t)(m - base_ms) >= (uint64_t)kSpanMs) return false;
+    return ns_of_ms(m) == ts;
+  }
+  __host__ __device__ static EvRec8 make(int64_t ts, uint32_t r, bool first, uint32_t ev, int64_t base_ms) {
+    EvRec8 v;
+    v.w = ((uint64_t)(ms_of(ts) - base_ms) << kMsShift) | ((uint64_t)(r & ((1u << kRuleBits) - 1)) << kRuleShift) |
+          ((uint64_t)(first ? 1u : 0u) << kEvBits) | (ev & kEvMask);
     return v;
   }
 };

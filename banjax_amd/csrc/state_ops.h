@@ -876,7 +876,7 @@ struct NewTables {
 // batch bind again so that it may cache again.
 // totals != nullptr (a rebuild: expiry, import): the entries changed too, so
 // the counters {ips, arena bytes, states} are set on the device and the host
-// and sort2_hold starts over, as bjx_state_clear does.  nullptr (growth): the
+// and sort2_hold and rec_hold start over, as bjx_state_clear does.  nullptr (growth): the
 // same entries under the same ids, the counters stand.
 void install(bjx_engine *e, NewTables &nw, const uint64_t *totals) {
   State &S = e->S;
@@ -903,6 +903,7 @@ void install(bjx_engine *e, NewTables &nw, const uint64_t *totals) {
   nw.own.take();
   if (!totals) return;
   e->sort2_hold = 0;
+  e->rec_hold = 0;
   hipLaunchKernelGGL(k_exp_counters, dim3(1), dim3(64), 0, e->stream, S.counters, totals[0], totals[1], totals[2]);
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(e->stream));
@@ -1174,6 +1175,7 @@ extern "C" int bjx_state_clear(bjx_engine *e) {
     State &S = e->S;
     HIP_OK(hipDeviceSynchronize());  // nothing of an earlier batch may land after the clear
     e->sort2_hold = 0;
+    e->rec_hold = 0;
     clear_tables(e->stream, S.ip, S.ip_first, S.ip_st, e->ip_cap, S.st, e->st_cap);
     HIP_OK(hipMemsetAsync(S.counters, 0, kCounterBytes, e->stream));
     HIP_OK(hipStreamSynchronize(e->stream));

@@ -257,11 +257,11 @@ class Engine:
     PHASES = ("count", "scan", "resolve", "emit", "capacity", "ip_state_claim", "sort_apply", "trips", "exchange")
 
     def scan_stats(self):
-        out = (C.c_uint64 * 12)()
-        _lib.lib().bjx_debug_scan_stats(self._h, out, 12)
+        out = (C.c_uint64 * 13)()
+        _lib.lib().bjx_debug_scan_stats(self._h, out, 13)
         return {"pair_filter_hits": out[0], "literal_hits": out[1], "fallback_lines": out[2], "scan_image_bytes": out[3],
                 "dfa_jobs": out[4], "ip_table_slots": out[5], "ips": out[6], "state_table_slots": out[7], "states": out[8],
-                "gram_table_hits": out[9], "grouping": out[10], "long_runs": out[11]}
+                "gram_table_hits": out[9], "grouping": out[10], "long_runs": out[11], "record_bytes": out[12]}
 
     def state_stats(self):
         """Occupancy of the HBM rate-limit tables (bjx_state_stats_get)."""
@@ -321,6 +321,11 @@ class Engine:
         """Test hook: the two-level rate-limit grouping uses `bits` high slot
         bits (1..16; 0 = the default 16), from the next batch."""
         self._check(_lib.lib().bjx_debug_set_bucket_bits(self._h, bits), "debug_set_bucket_bits")
+
+    def debug_set_rec8_max_events(self, max_events: int):
+        """Test hook: the 8-byte event records only for batches of at most
+        max_events events (0 = the default 2^28), from the next batch."""
+        self._check(_lib.lib().bjx_debug_set_rec8_max_events(self._h, max_events), "debug_set_rec8_max_events")
 
     def debug_state_slots(self, ips, names):
         """Test hook: the state-table slot of each (ips[k], names[k]) state, -1

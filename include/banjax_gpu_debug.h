@@ -50,7 +50,8 @@ size_t bjx_debug_kernel_ms(bjx_engine *e, double *out, size_t cap);
    tables: IP slots, IPs, state slots, states; then gram table hits, the
    rate-limit grouping (0: full sort by state slot; else two-level, 1 + the
    events of its oversized buckets), rate-limit runs that crossed a k_apply
-   chunk (k_long_runs) (returns the count, 12) */
+   chunk (k_long_runs), the bytes of the event records the rate-limit stage
+   sorted (8, 12 or 16) (returns the count, 13) */
 size_t bjx_debug_scan_stats(bjx_engine *e, uint64_t *out, size_t cap);
 /* Test hook: IP hashes become (hash & mask) | 1 (0 = off), so distinct IPs
    share 64-bit hashes and the exact collision path of the IP table runs. */
@@ -70,6 +71,20 @@ int bjx_debug_set_slot_cache(bjx_engine *e, int on);
    k_bucket_apply can run at without a table of 2^(16 + L) slots.  Unused, the
    same kernels run with the same arguments as without the hook. */
 int bjx_debug_set_bucket_bits(bjx_engine *e, uint32_t bits);
+/* Test hook: the 8-byte event records are tried only for batches of at most
+   max_events rate-limit events (0 = the default, the 2^28 of the record's
+   event index field; more is BJX_ERR_ARG), from the next batch on. */
+int bjx_debug_set_rec8_max_events(bjx_engine *e, uint64_t max_events);
+/* Test hook (host only, no device): one event record of `form` bytes (8, 12 or
+   16) made from (ts, rule, first, ev) against `base` (ms for the 8-byte form, ns
+   for the 12-byte one, unused at 16) by the functions the kernels use.
+   out[0..4]: fits(ts, base), time(base), rule_id(), seen(), and the event index
+   read as the kernels after the sort read it (its word of the record and a
+   mask).  A record made of values that do not fit holds garbage, as on the
+   device, where the batch is claimed again.  bjx_debug_event_record_bits:
+   out[0..2] = the form's timestamp, rule and event index field widths. */
+int bjx_debug_event_record(uint32_t form, int64_t ts, uint32_t rule, int first, uint32_t ev, int64_t base, int64_t *out);
+int bjx_debug_event_record_bits(uint32_t form, uint32_t *out);
 /* Test hook: the counting passes of bjx_state_trim (over the state table and
    over the per-IP newest starts) launch at most max_blocks blocks (0 = the
    default cap), so that their grid-stride loops wrap on small inputs. */
