@@ -117,6 +117,7 @@ EXPORTS = [
     "bjx_state_query_groups", "bjx_node_state_query_groups",
     "bjx_batch_rule_stats", "bjx_rule_stats_total", "bjx_rule_stats_reset",
     "bjx_node_batch_rule_stats", "bjx_node_rule_stats_total", "bjx_node_rule_stats_reset",
+    "bjx_state_merge", "bjx_node_state_merge",
 ]
 
 
@@ -136,6 +137,24 @@ class SnapshotStats(C.Structure):
     """bjx_snapshot_stats: what one bjx_state_export / bjx_state_import moved."""
     _fields_ = [(k, C.c_uint64) for k in ("ips", "states", "names", "bytes", "ips_skipped", "states_skipped")] + \
                [("device_ms", C.c_double)]
+
+
+MERGE_NEWER, MERGE_KEEP, MERGE_REPLACE = 0, 1, 2
+MERGE_DRY_RUN = 1
+
+
+class MergeOptions(C.Structure):
+    """bjx_merge_options: which records of the snapshot a bjx_state_merge takes and who wins a conflict (24 B)."""
+    _fields_ = [("min_start_ns", C.c_int64), ("part", C.c_uint32), ("n_parts", C.c_uint32), ("policy", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class MergeStats(C.Structure):
+    """bjx_merge_stats: what one bjx_state_merge found, added, replaced and kept (136 B)."""
+    _fields_ = [(k, C.c_uint64) for k in ("snap_ips", "snap_states", "snap_names", "snap_bytes", "ips_before", "ips_added",
+                                            "ips_skipped", "states_before", "states_added", "states_replaced",
+                                            "states_kept", "states_skipped", "arena_bytes_before", "arena_bytes_after",
+                                            "device_bytes_before", "device_bytes_after")] + [("device_ms", C.c_double)]
 
 
 QUERY_BY_HITS, QUERY_BY_START, QUERY_MAX_ROWS = 0, 1, 65536
@@ -384,6 +403,9 @@ def lib():
     L.bjx_state_import.argtypes = [vp, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(SnapshotStats)]
     L.bjx_node_state_import.restype = C.c_int
     L.bjx_node_state_import.argtypes = [vp, C.c_char_p, C.c_uint64, C.POINTER(SnapshotStats)]
+    for name in ("bjx_state_merge", "bjx_node_state_merge"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = C.c_int, [vp, C.c_char_p, C.c_uint64, C.POINTER(MergeOptions), C.POINTER(MergeStats)]
     for name in ("bjx_state_query", "bjx_node_state_query"):
         f = getattr(L, name)
         f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(StateRows)]

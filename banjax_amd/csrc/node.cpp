@@ -1033,6 +1033,46 @@ extern "C" int bjx_node_state_import(bjx_node *n, const uint8_t *snap, uint64_t 
   });
 }
 
+// engine k merges part k of n.  As bjx_node_state_remove: every shard is asked
+// even when one fails, the first failure is returned, the shards done stay
+// done, and the caller repeats the call (every policy is idempotent)
+extern "C" int bjx_node_state_merge(bjx_node *n, const uint8_t *snap, uint64_t len, const bjx_merge_options *o,
+                                    bjx_merge_stats *out) {
+  if (!n || !snap || !o) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    if (o->part != 0 || o->n_parts != 1) fail(BJX_ERR_ARG, "bjx_node_state_merge: part / n_parts must be 0, 1 (engine k takes part k)");
+    const size_t N = n->parts.size();
+    bjx_merge_stats t{};
+    int first_rc = BJX_OK;
+    std::string first_msg;
+    for (size_t k = 0; k < N; ++k) {
+      bjx_engine *e = n->parts[k].e;
+      bjx_merge_options ok = *o;
+      ok.part = (uint32_t)k;
+      ok.n_parts = (uint32_t)N;
+      bjx_merge_stats s{};
+      const int rc = bjx_state_merge(e, snap, len, &ok, &s);
+      if (rc != BJX_OK) {
+        if (first_rc == BJX_OK) {
+          first_rc = rc;
+          first_msg = "engine " + std::to_string(k) + ": " + bjx_engine_last_error(e);
+        }
+        continue;
+      }
+      t.snap_ips = s.snap_ips; t.snap_states = s.snap_states; t.snap_names = s.snap_names; t.snap_bytes = s.snap_bytes;
+      t.ips_before += s.ips_before; t.ips_added += s.ips_added; t.ips_skipped += s.ips_skipped;
+      t.states_before += s.states_before; t.states_added += s.states_added; t.states_replaced += s.states_replaced;
+      t.states_kept += s.states_kept; t.states_skipped += s.states_skipped;
+      t.arena_bytes_before += s.arena_bytes_before; t.arena_bytes_after += s.arena_bytes_after;
+      t.device_bytes_before += s.device_bytes_before; t.device_bytes_after += s.device_bytes_after;
+      if (s.device_ms > t.device_ms) t.device_ms = s.device_ms;
+    }
+    if (first_rc != BJX_OK) fail(first_rc, first_msg);
+    if (out) *out = t;
+    return BJX_OK;
+  });
+}
+
 // every shard's answer to the same filter and limit, merged on the host
 // (state_query.h); with an ip filter the owning engine's answer alone
 extern "C" int bjx_node_state_query(bjx_node *n, const bjx_state_filter *f, bjx_state_rows *out) {

@@ -731,6 +731,163 @@ __global__ void k_imp_verify(uint64_t n_ips, const uint32_t *__restrict__ keep, 
   if (found != 1 || !own) err[0] = 1u;
 }
 
+// snapshot merge (bjx_state_merge): the import's checks and owner filter, then
+// every kept snapshot IP is looked up in the live IP table and every record of
+// one in the live state table, which gives each record a verdict.  The new IPs
+// (not held, bringing a record) are scanned into the ids and arena offsets
+// after the engine's; the union is built into new tables: the engine's slots
+// re-put as growth does, the new IPs placed as import does, the records put
+// or written over their key's slot by their verdict.
+constexpr uint8_t kMrgSkip = 0, kMrgAdd = 1, kMrgReplace = 2, kMrgKeep = 3, kMrgFill = 4;  // Fill: the key is held with valid == 0
+// per snapshot IP: eid[i] = the engine's id of a kept IP, kNone when it holds
+// none (k_imp_verify's lookup on the live table: masked hash, key16, arena
+// bytes past 15).  claim[id] takes the first snapshot index that finds id; a
+// second one is an IP twice in the snapshot: err[0]
+__global__ void k_mrg_find(uint64_t n_ips, const uint32_t *__restrict__ keep, const uint64_t *__restrict__ hash, uint64_t hmask,
+                           const uint64_t *__restrict__ ip_off, const uint8_t *__restrict__ bytes, State S, uint64_t e_ips,
+                           uint32_t *__restrict__ eid, uint32_t *__restrict__ claim, uint32_t *__restrict__ err) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_ips) return;
+  uint32_t id = kNone;
+  if (keep[i] && e_ips) {
+    const uint64_t a = ip_off[i];
+    const uint32_t len = (uint32_t)(ip_off[i + 1] - a);
+    const uint8_t *src = bytes + a;
+    const uint4 k16 = ip_key16_bytes(src, len);
+    const uint64_t h = hmask ? (hash[i] & hmask) | 1ull : hash[i];
+    uint64_t j = h & S.ip_mask;
+    for (uint64_t step = 0; step <= S.ip_mask; ++step) {
+      const IpSlot v = S.ip[j];
+      if (v.hash == 0) break;
+      if (v.hash == h && v.id < e_ips && key16_eq(v.key16, k16) &&
+          (len <= 15 || (S.ip_len[v.id] == len && bytes_eq(S.arena + S.ip_off[v.id], src, len)))) {
+        id = v.id;
+        break;
+      }
+      j = (j + 1) & S.ip_mask;
+    }
+    if (id != kNone && atomicCAS(&claim[id], kNone, (uint32_t)i) != kNone) err[0] = 1u;
+  }
+  eid[i] = id;
+}
+// per record: the owner and min_start filters, the live state of its key (the
+// probe stops at an empty key; valid == 0 is absent), the policy -> verdict[i];
+// brings[ip] = 1 for an IP with a record that is not skipped.  cnt[0..4] +=
+// skipped, added, replaced, kept, and the added ones that take a new slot (one
+// atomic per block and counter).  remap: snapshot name -> engine name id, ids
+// from e_names on are names the engine has not interned
+__global__ __launch_bounds__(kBlock) void k_mrg_rec(uint64_t n_states, const uint64_t *__restrict__ recs,
+                                                    const uint32_t *__restrict__ keep, const uint32_t *__restrict__ eid,
+                                                    const uint32_t *__restrict__ remap, uint32_t e_names, State S,
+                                                    int64_t min_start, uint32_t policy, uint8_t *__restrict__ verdict,
+                                                    uint32_t *__restrict__ brings, unsigned long long *__restrict__ cnt) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t v = kMrgSkip;
+  if (i < n_states) {
+    const uint64_t w = recs[3 * i];
+    const uint32_t ip = (uint32_t)w;
+    const int64_t hits = (int64_t)recs[3 * i + 1], start = (int64_t)recs[3 * i + 2];
+    if (keep[ip] && start >= min_start) {
+      brings[ip] = 1u;  // every writer stores the same value
+      v = kMrgAdd;
+      const uint32_t id = eid[ip], nm = remap[w >> 32];
+      if (id != kNone && nm < e_names) {
+        const uint64_t key = ((uint64_t)(id + 1) << 24) | nm;
+        uint64_t j = mix64(key) & S.st_mask;
+        for (uint64_t step = 0; step <= S.st_mask; ++step, j = (j + 1) & S.st_mask) {
+          const StSlot s = S.st[j];
+          if (s.key == 0) break;
+          if (s.key != key) continue;
+          if (!s.valid) {
+            v = kMrgFill;
+          } else {
+            const bool differs = s.hits != hits || s.start != start;
+            const bool wins = policy == BJX_MERGE_REPLACE ? differs
+                              : policy == BJX_MERGE_KEEP  ? false
+                                                          : start > s.start || (start == s.start && hits > s.hits);
+            v = wins ? kMrgReplace : kMrgKeep;
+          }
+          break;
+        }
+      }
+    }
+    verdict[i] = (uint8_t)v;
+  }
+  const bool in = i < n_states;
+  uint64_t n_skip = in && v == kMrgSkip, n_add = in && (v == kMrgAdd || v == kMrgFill), n_rep = in && v == kMrgReplace,
+           n_keep = in && v == kMrgKeep, n_slot = in && v == kMrgAdd, z = 0;
+  block_sum2(n_skip, n_add);
+  __syncthreads();  // thread 0 has read the first pair's partial sums
+  block_sum2(n_rep, n_keep);
+  __syncthreads();
+  block_sum2(n_slot, z);
+  if (threadIdx.x == 0) {
+    if (n_skip) atomicAdd(&cnt[0], (unsigned long long)n_skip);
+    if (n_add) atomicAdd(&cnt[1], (unsigned long long)n_add);
+    if (n_rep) atomicAdd(&cnt[2], (unsigned long long)n_rep);
+    if (n_keep) atomicAdd(&cnt[3], (unsigned long long)n_keep);
+    if (n_slot) atomicAdd(&cnt[4], (unsigned long long)n_slot);
+  }
+}
+// per snapshot IP over [0, n_ips] (the last entry 0): is[i] = 1 and klen[i] =
+// its bytes for an IP the engine does not hold that brings a record; cnt[5] +=
+// the IPs that bring one, held or not
+__global__ __launch_bounds__(kBlock) void k_mrg_new(uint64_t n_ips, const uint64_t *__restrict__ ip_off,
+                                                    const uint32_t *__restrict__ keep, const uint32_t *__restrict__ brings,
+                                                    const uint32_t *__restrict__ eid, uint32_t *__restrict__ is,
+                                                    uint64_t *__restrict__ klen, unsigned long long *__restrict__ cnt) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t n = 0, z = 0;
+  if (i <= n_ips) {
+    const bool br = i < n_ips && keep[i] && brings[i];
+    const bool nw = br && eid[i] == kNone;
+    is[i] = nw ? 1u : 0u;
+    klen[i] = nw ? ip_off[i + 1] - ip_off[i] : 0;
+    n = br ? 1 : 0;
+  }
+  block_sum2(n, z);
+  if (threadIdx.x == 0 && n) atomicAdd(&cnt[5], (unsigned long long)n);
+}
+// the scans' ranks -> final ids and arena offsets: nid[i] = the engine's id of
+// a held IP, e_ips + rank for a new one, kNone for the others; noff[i] += used
+__global__ void k_mrg_ids(uint64_t n_ips, const uint32_t *__restrict__ is, const uint32_t *__restrict__ eid, uint64_t e_ips,
+                          uint64_t used, uint32_t *__restrict__ nid, uint64_t *__restrict__ noff) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_ips) return;
+  nid[i] = eid[i] != kNone ? eid[i] : is[i] ? (uint32_t)(e_ips + nid[i]) : kNone;
+  noff[i] += used;
+}
+// per record, after the engine's states are in the new table: an added record
+// takes a slot (k_imp_st), a replacing or filling one is written over the slot
+// of its key; err[7]: that key is not there (never: k_mrg_rec found it)
+__global__ void k_mrg_put(uint64_t n_states, const uint64_t *__restrict__ recs, const uint8_t *__restrict__ verdict,
+                          const uint32_t *__restrict__ nid, const uint32_t *__restrict__ remap, StSlot *__restrict__ nt,
+                          uint64_t nmask, uint32_t *__restrict__ err) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_states) return;
+  const uint32_t v = verdict[i];
+  if (v == kMrgSkip || v == kMrgKeep) return;
+  const uint64_t w = recs[3 * i];
+  const uint32_t id = nid[(uint32_t)w];
+  if (id == kNone) { err[7] = 1u; return; }  // (a record that is not skipped made its IP held or new)
+  const uint64_t key = ((uint64_t)(id + 1) << 24) | remap[w >> 32];
+  const int64_t hits = (int64_t)recs[3 * i + 1], start = (int64_t)recs[3 * i + 2];
+  if (v == kMrgAdd) {
+    fresh_put_st(nt, nmask, key, hits, start, 1);
+    return;
+  }
+  uint64_t j = mix64(key) & nmask;
+  for (uint64_t step = 0; step <= nmask; ++step, j = (j + 1) & nmask) {
+    const uint64_t k = nt[j].key;
+    if (k == 0) break;
+    if (k == key) {
+      nt[j].hits = hits; nt[j].start = start; nt[j].valid = 1;
+      return;
+    }
+  }
+  err[7] = 1u;
+}
+
 // state query (RegexRateLimitStates.Get for one (ip, name))
 __global__ void k_state_get(State S, uint64_t h, const uint8_t *ip, uint32_t len, uint32_t name_id, int64_t *out) {
   out[0] = 0;
@@ -1645,6 +1802,198 @@ extern "C" int bjx_state_import(bjx_engine *e, const uint8_t *snap, uint64_t len
       stats->states_skipped = n_states - K.states;
       stats->device_ms = E.ms(0, 1) + E.ms(2, 3) + E.ms(4, 5);
     }
+    return BJX_OK;
+  });
+}
+
+// Merge into an engine that holds state: import's upload, checks and owner
+// filter; the lookups of the snapshot's IPs and keys against the live tables
+// and the verdicts (k_mrg_find, k_mrg_rec); the ids and arena offsets of the
+// new IPs behind the engine's; and, when a record is added or replaces one,
+// the union built into new tables and installed.  The live tables are only
+// read until then and nothing of the engine changes before every check has
+// passed -- the names are interned last -- so every failure leaves it as it
+// was.  A dry run builds and checks the new tables too and drops them.
+static_assert(sizeof(bjx_merge_options) == 24 && sizeof(bjx_merge_stats) == 136, "the merge structs of the C ABI");
+extern "C" int bjx_state_merge(bjx_engine *e, const uint8_t *snap, uint64_t len, const bjx_merge_options *o,
+                               bjx_merge_stats *out) {
+  if (!e || !snap || !o) return BJX_ERR_ARG;
+  return guarded(e, [&]() -> int {
+    if (e->batch_open) throw BjxError(BJX_ERR_ARG, "bjx_state_merge between bjx_match_batch and its bjx_finish_batch");
+    if (o->policy > BJX_MERGE_REPLACE) throw BjxError(BJX_ERR_ARG, "bjx_state_merge: unknown policy");
+    if (o->flags & ~(uint32_t)BJX_MERGE_DRY_RUN) throw BjxError(BJX_ERR_ARG, "bjx_state_merge: unknown flag bits");
+    const uint32_t part = o->part, n_parts = o->n_parts;
+    if (n_parts < 1 || n_parts > kMaxParts || part >= n_parts)
+      throw BjxError(BJX_ERR_ARG, "bjx_state_merge: part / n_parts out of range (n_parts 1..256, part < n_parts)");
+    const bool dry = (o->flags & BJX_MERGE_DRY_RUN) != 0;
+    HIP_OK(hipDeviceSynchronize());  // nothing of an earlier batch may land after the rebuild
+    State &S = e->S;
+    hipStream_t st = e->stream;
+    read_counters(e);
+    const uint64_t e_ips = e->host_counters[0], used = e->host_counters[1], e_st = e->host_counters[2];
+    if (e_ips >= bjx_snap::kMaxIps) throw BjxError(BJX_ERR_CAPACITY, "bjx_state_merge: the engine holds 2^31 distinct IPs or more");
+    bjx_snap::Layout L;
+    std::vector<std::string> names;
+    if (const char *why = bjx_snap::validate_host(snap, len, &L, &names))
+      throw BjxError(BJX_ERR_ARG, std::string("bjx_state_merge: ") + why);
+    const uint64_t n_ips = L.n_ips, n_states = L.n_states;
+    const uint32_t n_names = (uint32_t)L.n_names;
+    SnapEvents E;
+    E.create();
+
+    const uint64_t body = L.total - L.o_ip_off;
+    ExpAlloc tmp;
+    uint8_t *d_body = tmp.get<uint8_t>(body + 16);
+    Kept K(tmp, n_ips);  // keep[]: the new IPs
+    uint64_t *hash = tmp.get<uint64_t>(n_ips + 1);
+    uint32_t *own = tmp.get<uint32_t>(n_ips + 1), *eid = tmp.get<uint32_t>(n_ips + 1), *brings = tmp.get<uint32_t>(n_ips + 1);
+    uint32_t *claim = tmp.get<uint32_t>(e_ips + 1);
+    uint8_t *verdict = tmp.get<uint8_t>(n_states + 1);
+    uint32_t *d_used = tmp.get<uint32_t>(n_names + 1), *d_remap = tmp.get<uint32_t>(n_names + 1), *d_err = tmp.get<uint32_t>(8);
+    if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, "bjx_state_merge: no device memory for the snapshot");
+    const uint64_t *d_ipoff = reinterpret_cast<const uint64_t *>(d_body);
+    const uint8_t *d_ipb = d_body + (L.o_ips - L.o_ip_off);
+    const uint64_t *d_recs = reinterpret_cast<const uint64_t *>(d_body + (L.o_recs - L.o_ip_off));
+    snap_copy_in(e, d_body, snap + L.o_ip_off, body);
+
+    // the device checks of import: nothing else runs before they pass
+    HIP_OK(hipEventRecord(E.ev[0], st));
+    HIP_OK(hipMemsetAsync(d_err, 0, 32, st));
+    HIP_OK(hipMemsetAsync(d_used, 0, (n_names + 1) * 4, st));
+    hipLaunchKernelGGL(k_imp_check, dim3(grid_for(std::max(n_ips + 1, n_states))), dim3(kBlock), 0, st, n_ips, d_ipoff, L.ip_bytes,
+                       n_states, d_recs, n_names, d_used, d_err);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(E.ev[1], st));
+    uint32_t err[8] = {};
+    std::vector<uint32_t> h_used(n_names + 1, 0);
+    pin_get(e, err, d_err, 32);
+    pin_sync(e);
+    HIP_OK(hipMemcpy(h_used.data(), d_used, (n_names + 1) * 4, hipMemcpyDeviceToHost));
+    static const char *const kWhy[7] = {"", "ip_off: not monotone from 0", "ip_off: does not end at ip_bytes",
+                                        "records: ip index out of range", "records: name index out of range",
+                                        "records: not strictly ascending by (ip, name)", "records: an IP without a record"};
+    for (int c = 1; c < 7; ++c)
+      if (err[c]) throw BjxError(BJX_ERR_ARG, std::string("bjx_state_merge: ") + kWhy[c]);
+    for (uint32_t k = 0; k < n_names; ++k)
+      if (!h_used[k]) throw BjxError(BJX_ERR_ARG, "bjx_state_merge: names: a name no record uses");
+
+    // names -> this engine's ids; one it has not interned gets the id it will
+    // be interned under once everything has passed
+    const uint32_t e_names = (uint32_t)e->names.size();
+    std::vector<uint32_t> remap(n_names + 1, 0);
+    std::vector<uint32_t> fresh_names;
+    for (uint32_t k = 0; k < n_names; ++k) {
+      auto it = e->name_ids.find(names[k]);
+      if (it != e->name_ids.end()) {
+        remap[k] = it->second;
+      } else {
+        remap[k] = e_names + (uint32_t)fresh_names.size();
+        fresh_names.push_back(k);
+      }
+    }
+    if ((uint64_t)e_names + fresh_names.size() >= bjx_snap::kMaxNames)
+      throw BjxError(BJX_ERR_CAPACITY, "bjx_state_merge: the union would reach 2^24 rule names");
+    HIP_OK(hipMemcpyAsync(d_remap, remap.data(), (n_names + 1) * 4, hipMemcpyHostToDevice, st));
+
+    // per IP: hash, owner filter, the engine's id; per record: the verdict; the new IPs scanned
+    e->chk.ensure(8);
+    HIP_OK(hipEventRecord(E.ev[2], st));
+    HIP_OK(hipMemsetAsync(e->chk.p, 0, 64, st));
+    HIP_OK(hipMemsetAsync(brings, 0, (n_ips + 1) * 4, st));
+    HIP_OK(hipMemsetAsync(claim, 0xFF, (e_ips + 1) * 4, st));
+    hipLaunchKernelGGL(k_imp_ip, dim3(grid_for(n_ips + 1)), dim3(kBlock), 0, st, n_ips, d_ipoff, d_ipb, part, n_parts, own, K.klen,
+                       hash);
+    HIP_OK(hipGetLastError());
+    if (n_ips) {
+      hipLaunchKernelGGL(k_mrg_find, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, own, hash, e->dbg_hash_mask, d_ipoff, d_ipb,
+                         S, e_ips, eid, claim, d_err);
+      HIP_OK(hipGetLastError());
+    }
+    if (n_states) {
+      hipLaunchKernelGGL(k_mrg_rec, dim3(grid_for(n_states)), dim3(kBlock), 0, st, n_states, d_recs, own, eid, d_remap, e_names, S,
+                         o->min_start_ns, o->policy, verdict, brings, e->chk.p);
+      HIP_OK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_mrg_new, dim3(grid_for(n_ips + 1)), dim3(kBlock), 0, st, n_ips, d_ipoff, own, brings, eid, K.keep, K.klen,
+                       e->chk.p);
+    HIP_OK(hipGetLastError());
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, K.keep, K.nid, (int)(n_ips + 1), st); });
+    cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, K.klen, K.noff, (int)(n_ips + 1), st); });
+    HIP_OK(hipEventRecord(E.ev[3], st));
+    unsigned long long cnt[6] = {};
+    uint32_t new_ips32 = 0;
+    uint64_t new_bytes = 0;
+    pin_get(e, cnt, e->chk.p, 48);
+    pin_get(e, &new_ips32, K.nid + n_ips, 4);
+    pin_get(e, &new_bytes, K.noff + n_ips, 8);
+    pin_get(e, err, d_err, 32);
+    pin_sync(e);
+    if (err[0]) throw BjxError(BJX_ERR_ARG, "bjx_state_merge: ips: an IP appears twice in the snapshot");
+    const uint64_t new_ips = new_ips32, new_slots = cnt[4];
+    if (cnt[0] + cnt[1] + cnt[2] + cnt[3] != n_states || new_ips > n_ips || new_bytes > L.ip_bytes || new_slots > cnt[1] ||
+        cnt[5] > n_ips || cnt[5] < new_ips)
+      throw BjxError(BJX_ERR_DEVICE, "internal: merge counts exceed the snapshot");
+    if (e_ips + new_ips >= bjx_snap::kMaxIps) throw BjxError(BJX_ERR_CAPACITY, "bjx_state_merge: the union would reach 2^31 distinct IPs");
+
+    const uint64_t bytes_before = state_device_bytes(e->ip_cap, e->st_cap, S.arena_cap);
+    bjx_merge_stats r{};
+    r.snap_ips = n_ips; r.snap_states = n_states; r.snap_names = n_names; r.snap_bytes = len;
+    r.ips_before = e_ips; r.ips_added = new_ips; r.ips_skipped = n_ips - cnt[5];
+    r.states_before = e_st; r.states_skipped = cnt[0]; r.states_added = cnt[1]; r.states_replaced = cnt[2]; r.states_kept = cnt[3];
+    r.arena_bytes_before = used; r.arena_bytes_after = used + new_bytes;
+    r.device_bytes_before = r.device_bytes_after = bytes_before;
+    r.device_ms = E.ms(0, 1) + E.ms(2, 3);
+    if (cnt[1] + cnt[2] == 0) {  // nothing to change: the tables were only read
+      if (out) *out = r;
+      return BJX_OK;
+    }
+
+    // the union in new tables: the growth rule on its counts, never below the
+    // present capacities; allocated before the old go
+    const uint64_t tot_ips = e_ips + new_ips, tot_bytes = used + new_bytes, tot_st = e_st + new_slots;
+    NewTables nw(clamp_cap(table_cap_for(tot_ips), e->ip_cap, kNoCeiling), clamp_cap(table_cap_for(tot_st), e->st_cap, kNoCeiling),
+                 clamp_cap(arena_cap_for(tot_bytes), S.arena_cap, kNoCeiling),
+                 "bjx_state_merge: no device memory for the new tables (state unchanged)");
+    // born: as import's, non-zero and below every later batch's epoch
+    const uint32_t born = e->epoch ? e->epoch : 1;
+    HIP_OK(hipEventRecord(E.ev[4], st));
+    nw.clear(st);
+    if (used) HIP_OK(hipMemcpyAsync(nw.arena, S.arena, used, hipMemcpyDeviceToDevice, st));
+    if (e_ips) {
+      HIP_OK(hipMemcpyAsync(nw.ip_off, S.ip_off, e_ips * 8, hipMemcpyDeviceToDevice, st));
+      HIP_OK(hipMemcpyAsync(nw.ip_len, S.ip_len, e_ips * 4, hipMemcpyDeviceToDevice, st));
+    }
+    hipLaunchKernelGGL(k_rehash_ip, dim3(grid_for(e->ip_cap)), dim3(kBlock), 0, st, e->ip_cap, S.ip, nw.ip, nw.ip_cap - 1);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_rehash_st, dim3(grid_for(e->st_cap)), dim3(kBlock), 0, st, e->st_cap, S.st, nw.st, nw.st_cap - 1);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_mrg_ids, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, K.keep, eid, e_ips, used, K.nid, K.noff);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_imp_place, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, K.keep, K.nid, K.noff, hash, e->dbg_hash_mask,
+                       d_ipoff, d_ipb, born, tot_ips, nw.arena, nw.arena_cap, nw.ip_off, nw.ip_len, nw.ip, nw.ip_cap - 1);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_mrg_put, dim3(grid_for(n_states)), dim3(kBlock), 0, st, n_states, d_recs, verdict, K.nid, d_remap, nw.st,
+                       nw.st_cap - 1, d_err);
+    HIP_OK(hipGetLastError());
+    // the duplicate check for the IPs the engine did not hold: each is found once, under its own id
+    hipLaunchKernelGGL(k_imp_verify, dim3(grid_for(n_ips)), dim3(kBlock), 0, st, n_ips, K.keep, K.nid, hash, e->dbg_hash_mask,
+                       d_ipoff, d_ipb, tot_ips, nw.ip, nw.ip_cap - 1, nw.ip_off, nw.ip_len, nw.arena, d_err);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(E.ev[5], st));
+    pin_get(e, err, d_err, 32);
+    pin_sync(e);
+    if (err[0]) throw BjxError(BJX_ERR_ARG, "bjx_state_merge: ips: an IP appears twice in the snapshot");
+    if (err[7]) throw BjxError(BJX_ERR_DEVICE, "internal: merge lost the slot of a held key");
+    r.device_ms += E.ms(4, 5);
+    if (!dry) {
+      for (uint32_t k : fresh_names)
+        if (intern_name(e, names[k]) != remap[k]) throw BjxError(BJX_ERR_DEVICE, "internal: merge name ids moved");
+      e->epoch = born;
+      r.device_bytes_after = state_device_bytes(nw.ip_cap, nw.st_cap, nw.arena_cap);
+      const uint64_t totals[3] = {tot_ips, tot_bytes, tot_st};
+      install(e, nw, totals);
+    }
+    if (out) *out = r;
     return BJX_OK;
   });
 }

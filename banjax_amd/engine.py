@@ -415,6 +415,27 @@ class Engine:
         self._check(_lib.lib().bjx_state_import(self._h, blob, len(blob), part, n_parts, C.byref(st)), "state_import")
         return {k: getattr(st, k) for k, _ in _lib.SnapshotStats._fields_}
 
+    _merge = "bjx_state_merge"
+
+    def state_merge(self, blob: bytes, policy=_lib.MERGE_NEWER, min_start_ns: int = INT64_MIN, part: int = 0,
+                    n_parts: int = 1, dry_run: bool = False) -> dict:
+        """Fold a snapshot into this engine, which may hold state
+        (bjx_state_merge; banjax_amd/state_merge.py is its model).  policy:
+        _lib.MERGE_NEWER (the larger (start, hits) wins a key both sides hold),
+        _KEEP (the engine's record stays) or _REPLACE (the snapshot's wins), or
+        "newer" / "keep" / "replace".  Snapshot records that started before
+        min_start_ns, and with n_parts > 1 the IPs `part` does not own, are
+        skipped.  The engine's IPs keep their order; new ones follow in
+        snapshot order.  Nothing to add or replace: the engine is left exactly
+        as it was.  dry_run: the counts as the real call would report them,
+        nothing changed.  Returns the bjx_merge_stats fields."""
+        policy = {"newer": _lib.MERGE_NEWER, "keep": _lib.MERGE_KEEP, "replace": _lib.MERGE_REPLACE}.get(policy, policy)
+        o = _lib.MergeOptions(min_start_ns, part, n_parts, policy, _lib.MERGE_DRY_RUN if dry_run else 0)
+        st = _lib.MergeStats()
+        blob = bytes(blob)
+        self._check(getattr(_lib.lib(), self._merge)(self._h, blob, len(blob), C.byref(o), C.byref(st)), "state_merge")
+        return {k: getattr(st, k) for k, _ in _lib.MergeStats._fields_}
+
     _query = "bjx_state_query"
 
     def state_query(self, ip=None, name=None, min_hits: int = INT64_MIN, min_start_ns: int = INT64_MIN,
@@ -704,6 +725,9 @@ class Node:
     _snap = "bjx_node_state"
     state_export_bound = Engine.state_export_bound
     state_export = Engine.state_export  # the shards merged into one snapshot, IPs engine-major
+
+    _merge = "bjx_node_state_merge"
+    state_merge = Engine.state_merge  # engine k merges the IPs it owns (part, n_parts stay 0, 1); stats summed
 
     _query = "bjx_node_state_query"
     state_query = Engine.state_query  # every shard's answer merged, IPs engine-major; an ip filter asks its owner only

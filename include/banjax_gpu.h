@@ -362,6 +362,114 @@ int bjx_state_export(bjx_engine *e, int64_t min_start_ns, uint8_t *out, uint64_t
                      bjx_snapshot_stats *stats);
 int bjx_state_import(bjx_engine *e, const uint8_t *snap, uint64_t len, uint32_t part, uint32_t n_parts,
                      bjx_snapshot_stats *stats);
+/* ---- Merge: fold a snapshot into an engine that holds state (no counterpart
+   in the reference).  Import needs an empty engine; this call is for the host
+   that has already processed batches when a snapshot reaches it: it takes over
+   a leaving host's traffic (failover, consolidation), it began tailing before
+   the snapshot of its previous life was read back (late restore), or a live
+   node is re-sharded onto.
+
+   Snapshot: a version-1 blob, validated exactly as bjx_state_import validates
+   it (the same host and device checks, the same messages).
+
+   Which side counts.  On the engine the states with valid != 0 -- exactly
+   what bjx_state_export writes; a slot claimed with valid == 0 is absent.  From
+   the snapshot the records of the IPs the part owns ((hash_bytes(ip) >> 32) %
+   n_parts == part, as import; 0, 1: all) whose interval_start_ns >=
+   min_start_ns (INT64_MIN: all).  The others are skipped.
+
+   Conflict.  A key is (IP bytes, rule name bytes); the policy decides a key
+   both sides hold.
+     BJX_MERGE_NEWER    the record with the larger interval_start_ns wins; on
+                        equal starts the larger hits (signed); equal in both:
+                        nothing changes.  That is the lexicographic maximum of
+                        (start, hits), so merging states is idempotent,
+                        commutative and associative.  Why this rule: a later
+                        start means that side saw the older window end, and on a
+                        shared window the larger count is the closer one to the
+                        count over the union of the two streams.  No merge of two
+                        fixed-window counters reproduces the union stream
+                        exactly (each side has counted only its own lines, and
+                        the window a stream opens depends on its own first
+                        line); in particular a count that a trip set back to 0
+                        loses to the pre-trip count of the same window.
+     BJX_MERGE_KEEP     the engine's record stays; the snapshot only fills gaps.
+     BJX_MERGE_REPLACE  the snapshot's record wins (counted in states_replaced
+                        only when it differs).
+   A key only the snapshot holds is added under every policy.
+
+   Order and ids.  The engine's IPs keep their ids and their first-seen order.
+   A snapshot IP the engine does not hold that brings at least one record is
+   appended after them, in snapshot order, under the next dense ids; one all of
+   whose records are skipped is not added.  Names are interned into this
+   engine, as import does.
+
+   Equivalence.  Everything a caller can observe afterwards equals an engine
+   that imported the snapshot M = merge_model(export(engine before), snap,
+   options) (banjax_amd/state_merge.py is that model): bjx_state_get / _len /
+   _dump / _query* / _export -- export is canonical, so export(after) == M byte
+   for byte -- and every later RuleResult's seen_ip, match_type and exceeded,
+   trips and bans.
+
+   Nothing to change (every record skipped, or every conflict keeps the
+   engine's record; merging an engine's own export is this case): the engine is
+   left exactly as it was.  No rebuild runs, no table changes size, rehashes is
+   unchanged and the stats' after values equal their before values.
+
+   BJX_MERGE_DRY_RUN: every count and arena_bytes_after come back as the real
+   call would report them (and the errors it would return), nothing changes,
+   device_bytes_after = device_bytes_before.
+
+   Tables.  One path: the union is built into new tables -- the engine's
+   entries re-put as growth does, the new IPs and records as import does --
+   and swapped in; everything a change of tables resets is reset (the hot-name
+   slot cache too).  They are sized by the growth rule on the union counts,
+   never below the present capacities: a merge never shrinks.  The new tables
+   are allocated before the old ones are freed: BJX_ERR_NOMEM leaves the state
+   untouched and usable.  rehashes does not count a merge.  The rebuild makes a
+   merge cost O(engine state + snapshot), whatever the share that changes.
+   Temporary device memory: the snapshot from its ip_off section on, 44 bytes
+   per snapshot IP and 1 per record, 4 bytes per held IP, and (dry run
+   included) the new tables next to the old.
+
+   Errors.  BJX_ERR_ARG, the engine unchanged in every case: a NULL handle,
+   snap or o; an unknown policy or unknown flag bits; part / n_parts out of
+   range (n_parts 1..256, part < n_parts); a call between bjx_match_batch and
+   its bjx_finish_batch*; a snapshot that fails a check (the message names it);
+   an IP that appears twice in the snapshot, whether or not the engine holds it
+   (seen among the IPs the part owns that bring a record or that the engine
+   holds).  BJX_ERR_CAPACITY: the union would reach 2^31 IPs or 2^24 names.
+   out may be NULL.  Takes the engine lock like the other bjx_state_* calls.
+
+   bjx_node_state_merge waits for the node batch; engine k merges with part =
+   k, n_parts = size, so the caller's part / n_parts must be 0, 1
+   (BJX_ERR_ARG).  Counts and bytes are summed, the snap_* fields reported
+   once, device_ms is the slowest shard's; a dry run is dry on every shard.
+   Every shard is asked even when one fails: the first failure is returned and
+   the shards already done stay done.  Every policy is idempotent, so the
+   caller repeats the call, as with bjx_node_state_remove. */
+enum bjx_merge_policy { BJX_MERGE_NEWER = 0, BJX_MERGE_KEEP = 1, BJX_MERGE_REPLACE = 2 };
+enum bjx_merge_flags { BJX_MERGE_DRY_RUN = 1 };
+typedef struct bjx_merge_options { /* 24 B */
+  int64_t min_start_ns;   /* snapshot records with interval_start_ns below this are skipped (INT64_MIN: none) */
+  uint32_t part, n_parts; /* as bjx_state_import: only IPs with (hash_bytes(ip) >> 32) % n_parts == part; 0, 1: all */
+  uint32_t policy;        /* enum bjx_merge_policy */
+  uint32_t flags;         /* enum bjx_merge_flags */
+} bjx_merge_options;
+typedef struct bjx_merge_stats { /* 136 B */
+  uint64_t snap_ips, snap_states, snap_names, snap_bytes; /* what the snapshot holds */
+  uint64_t ips_before, ips_added;                          /* IPs the engine did not hold and now does */
+  uint64_t ips_skipped;     /* snapshot IPs that brought nothing: other part, or every record skipped */
+  uint64_t states_before;
+  uint64_t states_added;    /* key not held (or held with valid == 0) */
+  uint64_t states_replaced; /* key held, the snapshot's record won and differs */
+  uint64_t states_kept;     /* key held, the engine's record stays (lost, or equal) */
+  uint64_t states_skipped;  /* other part, or below min_start_ns; the four add up to snap_states */
+  uint64_t arena_bytes_before, arena_bytes_after;
+  uint64_t device_bytes_before, device_bytes_after; /* as bjx_state_stats.device_bytes */
+  double device_ms;                                 /* HIP events, copies excluded */
+} bjx_merge_stats;
+int bjx_state_merge(bjx_engine *e, const uint8_t *snap, uint64_t len, const bjx_merge_options *o, bjx_merge_stats *out);
 /* ---- Query: top-K, counts and Get(ip) over the state where it lives.
    bjx_state_dump (RegexRateLimitStates.String, the /rate_limit_states route,
    http_server.go:193-198) is text of every state and bjx_state_get answers one
@@ -893,6 +1001,13 @@ uint64_t bjx_node_state_export_bound(bjx_node *n);
 int bjx_node_state_export(bjx_node *n, int64_t min_start_ns, uint8_t *out, uint64_t cap, uint64_t *len,
                           bjx_snapshot_stats *stats);
 int bjx_node_state_import(bjx_node *n, const uint8_t *snap, uint64_t len, bjx_snapshot_stats *stats);
+/* bjx_state_merge over the node (its contract is with bjx_state_merge): engine
+   k merges part k of size, so o->part, o->n_parts must be 0, 1.  Counts and
+   bytes summed, snap_* once, device_ms the slowest shard's.  Every shard is
+   asked even when one fails; the first failure is returned, the shards done
+   stay done, and the caller repeats the call (every policy is idempotent).
+   Waits for the node batch.  out may be NULL. */
+int bjx_node_state_merge(bjx_node *n, const uint8_t *snap, uint64_t len, const bjx_merge_options *o, bjx_merge_stats *out);
 /* bjx_state_query over the node.  Every shard answers the same filter and
    limit and the host merges the answers: an IP lives on one engine and the
    global first-seen order is the engine-major order of bjx_node_state_dump, so
