@@ -6,6 +6,7 @@ include/banjax_gpu.h; this package is the host surface mirroring the
 reference's Go types (config schema, consumeLine, RegexRateLimitStates,
 Banner / DynamicDecisionLists).
 """
+from . import state_names  # the model and the reload helper of state_query_names (state_names.orphans)
 from .config import (ALLOW, CHALLENGE, IPTABLES_BLOCK, NGINX_BLOCK, Config, ConfigError, RegexWithRate, Ruleset,
                      decision_string, parse_decision)
 from .engine import BatchOutput, Engine, Node
@@ -17,6 +18,6 @@ __all__ = [
     "ALLOW", "CHALLENGE", "NGINX_BLOCK", "IPTABLES_BLOCK", "Config", "ConfigError", "RegexWithRate", "Ruleset",
     "decision_string", "parse_decision", "Engine", "Node", "BatchOutput", "Banner", "MockBanner", "DynamicDecisionLists",
     "ConsumeLineResult", "RuleResult", "RateLimitResult", "RegexRateLimiter", "RegexRateLimitStates", "consume_line", "Zone",
-    "expire_cutoff_ns",
+    "expire_cutoff_ns", "state_names",
     "LogTailer", "TailBatch", "TailStopped", "run_log_tailer",
 ]

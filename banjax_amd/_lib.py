@@ -115,6 +115,7 @@ EXPORTS = [
     "bjx_state_query_nets", "bjx_node_state_query_nets", "bjx_state_remove_nets", "bjx_node_state_remove_nets",
     "bjx_state_trim", "bjx_node_state_trim",
     "bjx_state_query_groups", "bjx_node_state_query_groups",
+    "bjx_state_query_names", "bjx_node_state_query_names",
     "bjx_batch_rule_stats", "bjx_rule_stats_total", "bjx_rule_stats_reset",
     "bjx_node_batch_rule_stats", "bjx_node_rule_stats_total", "bjx_node_rule_stats_reset",
     "bjx_state_merge", "bjx_node_state_merge",
@@ -227,6 +228,30 @@ class StateGroups(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_matched", "n_ips_matched", "n_ips_unparsed", "n_states_unparsed", "n_groups",
                                             "n_groups_min", "n_rows")] + \
                [("rows", C.POINTER(GroupRow)), ("device_ms", C.c_double)]
+
+
+NAMES_BY_STATES, NAMES_BY_HITS, NAMES_BY_MAX_HITS, NAMES_BY_NEWEST, NAMES_BY_NAME = 0, 1, 2, 3, 4
+NAMES_MAX_ROWS = 65536
+NAMES_HIST = 16
+
+
+class NamesSpec(C.Structure):
+    """bjx_names_spec: the order and the cut of a bjx_state_query_names (16 B)."""
+    _fields_ = [("order", C.c_uint32), ("limit", C.c_uint32), ("min_states", C.c_uint64)]
+
+
+class NameRow(C.Structure):
+    """bjx_name_row: one rule name of the answer (184 B)."""
+    _fields_ = [("name_off", C.c_uint64), ("name_len", C.c_uint32), ("_pad", C.c_uint32), ("n_states", C.c_uint64),
+                ("hits_sum", C.c_int64), ("max_hits", C.c_int64), ("newest_start_ns", C.c_int64),
+                ("oldest_start_ns", C.c_int64), ("hist", C.c_uint64 * NAMES_HIST)]
+
+
+class StateNames(C.Structure):
+    """bjx_state_names: counts and the first rows of a bjx_state_query_names (72 B)."""
+    _fields_ = [(k, C.c_uint64) for k in ("n_matched", "n_ips_matched", "n_names", "n_names_min", "n_rows")] + \
+               [("rows", C.POINTER(NameRow)), ("bytes", C.POINTER(C.c_uint8)), ("n_bytes", C.c_uint64),
+                ("device_ms", C.c_double)]
 
 
 class RuleStat(C.Structure):
@@ -425,6 +450,13 @@ def lib():
     for name in ("bjx_state_query_groups", "bjx_node_state_query_groups"):
         f = getattr(L, name)
         f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(GroupSpec), C.POINTER(StateGroups)]
+    for name in ("bjx_state_query_names", "bjx_node_state_query_names"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = C.c_int, [vp, C.POINTER(StateFilter), C.POINTER(NamesSpec), C.POINTER(StateNames)]
+    L.bjx_debug_set_names.restype = C.c_int
+    L.bjx_debug_set_names.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.bjx_debug_names_info.restype = C.c_int
+    L.bjx_debug_names_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]
     L.bjx_debug_groups_tile.restype = C.c_uint32
     L.bjx_debug_groups_tile.argtypes = []
     L.bjx_debug_set_trim_grid.restype = C.c_int

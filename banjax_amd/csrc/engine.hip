@@ -50,6 +50,7 @@
 #include "state_nets.h"
 #include "state_trim.h"
 #include "state_groups.h"
+#include "state_names.h"
 
 using namespace bjx;
 
@@ -5247,6 +5248,11 @@ struct bjx_engine {
   HostBuf<uint8_t> qry_bytes;
   std::vector<uint64_t> qry_net_ips;  // bjx_state_query_nets: the last answer's net_ips
   std::vector<bjx_group_row> grp_rows;  // bjx_state_query_groups: the last answer's rows
+  std::vector<bjx_name_row> nam_rows;  // bjx_state_query_names: the last answer's rows and their names
+  std::vector<uint8_t> nam_bytes;
+  uint32_t dbg_nam_lds_names = 0, dbg_nam_blocks = 0;  // bjx_debug_set_names (0 = default)
+  uint32_t nam_lds_set = 0;  // dynamic LDS k_nam_scan was last raised to
+  int nam_path = 0;          // where the last names query binned: 0 nothing launched, 1 LDS, 2 global
 
   // per-rule counts of the batches closed with BJX_RULE_STATS (rule_stats.h);
   // nothing here is allocated or created before the first such batch

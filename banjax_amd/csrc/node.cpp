@@ -49,6 +49,7 @@
 #include "state_trim.h"
 #include "state_nets.h"
 #include "state_groups.h"
+#include "state_names.h"
 
 namespace {
 
@@ -132,6 +133,8 @@ struct bjx_node {
   std::vector<uint8_t> q_bytes;
   std::vector<uint64_t> q_net_ips;  // and of the last bjx_node_state_query_nets, the summed net_ips
   std::vector<bjx_group_row> g_rows;  // the last bjx_node_state_query_groups' rows
+  std::vector<bjx_name_row> nm_rows;  // the last bjx_node_state_query_names' rows and their names
+  std::vector<uint8_t> nm_bytes;
   // per-rule counts (BJX_RULE_STATS): the engines' arrays summed, for the last
   // batch and over every flagged batch since its ruleset came into use
   bool rs_counted = false;
@@ -1249,6 +1252,35 @@ extern "C" int bjx_node_state_query_groups(bjx_node *n, const bjx_state_filter *
     std::vector<bjx_groups::Rec> merged;
     if (!bjx_groups::merge(lists, bjx_groups::kGroupsNodeMax, &merged)) fail(BJX_ERR_CAPACITY, too_many);
     bjx_groups::finish(merged, *g, total, out, &n->g_rows);
+    return BJX_OK;
+  });
+}
+
+// every shard's complete name list, merged by name bytes on the host;
+// min_states, the order and the limit only then (state_names.h: merge, finish)
+extern "C" int bjx_node_state_query_names(bjx_node *n, const bjx_state_filter *f, const bjx_names_spec *s,
+                                          bjx_state_names *out) {
+  if (!n || !f || !s || !out) return BJX_ERR_ARG;
+  return guarded(n, [&]() -> int {
+    memset(out, 0, sizeof *out);
+    if (const char *why = bjx_names::check_filter(f)) fail(BJX_ERR_ARG, std::string("bjx_node_state_query_names: ") + why);
+    if (const char *why = bjx_names::check_spec(s)) fail(BJX_ERR_ARG, std::string("bjx_node_state_query_names: ") + why);
+    const char *const too_many = "bjx_node_state_query_names: more than 2^20 names on the shards together";
+    std::vector<std::vector<bjx_names::Item>> lists(n->parts.size());
+    bjx_names::Counts total;
+    uint64_t held = 0;
+    for (size_t k = 0; k < n->parts.size(); ++k) {
+      bjx_engine *e = n->parts[k].e;
+      bjx_names::Counts c;
+      const int rc = bjx_names_list(e, f, s, bjx_names::kNamesNodeMax - held, &lists[k], &c);
+      if (rc == BJX_ERR_CAPACITY) fail(rc, too_many);
+      if (rc != BJX_OK) fail(rc, "engine " + std::to_string(k) + ": " + bjx_engine_last_error(e));
+      held += lists[k].size();
+      bjx_names::add(&total, c);
+    }
+    std::vector<bjx_names::Item> merged;
+    if (!bjx_names::merge(lists, bjx_names::kNamesNodeMax, &merged)) fail(BJX_ERR_CAPACITY, too_many);
+    bjx_names::finish(std::move(merged), *s, total, out, &n->nm_rows, &n->nm_bytes);
     return BJX_OK;
   });
 }

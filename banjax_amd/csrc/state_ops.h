@@ -3025,3 +3025,307 @@ int bjx_groups_list(bjx_engine *e, const bjx_state_filter *f, const bjx_group_sp
   if (!e || !f || !g || !list || !counts) return BJX_ERR_ARG;
   return guarded(e, [&]() -> int { return groups_locked(e, f, g, nullptr, room, list, counts); });
 }
+
+// ---- names: bjx_state_query_names (the checks, the histogram bucket, the
+// record per name, the rows' order, the node's merge: state_names.h).  One
+// pass over the state table (k_nam_scan, k_qry_scan's shape: 64-bit indices,
+// kNamItems slots per thread and pass, a capped grid) stores keep[ip id] = 1
+// for every selected state -- a hipCUB sum of keep[] is n_ips_matched, as in
+// the query -- and adds the state into the accumulators of its name: one
+// histogram bin by bjx_names::bucket(hits), the hits sum, and three maxima
+// (the largest hits, the newest start, the complement of the oldest start, all
+// as unsigned keys, so that zeroed memory is the empty accumulator).  The
+// count of a name is the sum of its bins and is never added on its own.
+// LDS path: while all interned names fit, the accumulators are LDS arrays
+// indexed by name id, [field][name] so that neighbouring names fall into
+// neighbouring banks: 16 u32 bins and four 64-bit words, 96 bytes a name.
+// A maximum is read before it is raised (it only grows: a read that already
+// covers the state spares the atomic).  At its end a block adds its non-empty
+// bins to the global records, at most one global atomic per field, name and
+// block.  Global path: the same adds, straight to the global records.
+// k_nam_compact appends the records with a count densely (block_alloc) and
+// fills in the count and the name id; the host copies exactly those.
+namespace {
+
+constexpr int kNamBlock = 1024;  // threads of k_nam_scan: with 96 B of LDS a name a CU holds one block, which then brings 16 waves
+constexpr int kNamItems = 4;     // state slots per thread and pass
+constexpr uint32_t kNamLdsBytes = 96;                                // LDS per name: 4 x 8 + 16 x 4
+constexpr uint32_t kNamLdsMax = 128 * 1024;                          // dynamic LDS a block may ask for (of gfx950's 160 KiB; rule_stats.h takes the same)
+constexpr uint32_t kNamLdsNames = kNamLdsMax / kNamLdsBytes;         // names the LDS path takes: 1,365
+constexpr unsigned kNamGridLds = 256;    // blocks at most on the LDS path: one per CU, each flushes its bins once
+constexpr unsigned kNamGridGlobal = 2048;  // blocks at most on the global path (nothing to flush)
+static_assert(sizeof(bjx_name_row) == 184 && sizeof(bjx_names_spec) == 16 && sizeof(bjx_state_names) == 72,
+              "the names structs of the C ABI");
+
+// raise a maximum that only grows.  The plain read may be stale while other
+// waves raise the word with atomics, but a stale value is never above the
+// current one: the read can only fail to spare an atomicMax, it can never
+// skip an update that was needed.
+__device__ __forceinline__ void nam_max(unsigned long long *p, unsigned long long v) {
+  if (*reinterpret_cast<volatile unsigned long long *>(p) < v) atomicMax(p, v);
+}
+
+// grid-stride over the state table; sel != NULL: only the states of IPs with
+// sel[id] set.  g[n_names] zeroed before; keep[ip id] = 1 for a selected
+// state; tot[0] += selected states (one atomic per block).  LDS: the dynamic
+// LDS holds n_names * kNamLdsBytes bytes.
+template <bool LDS>
+__global__ __launch_bounds__(kNamBlock) void k_nam_scan(uint64_t st_cap, const StSlot *__restrict__ st, QFilter F, uint64_t n_ips,
+                                                        uint32_t n_names, const uint32_t *__restrict__ sel,
+                                                        uint32_t *__restrict__ keep, bjx_names::Rec *__restrict__ g,
+                                                        unsigned long long *__restrict__ tot) {
+  extern __shared__ unsigned long long nam_lds[];
+  __shared__ unsigned long long s_n;
+  unsigned long long *const l64 = nam_lds;                                            // [4][n_names]: hits, max_hits, newest, oldest_inv
+  uint32_t *const l32 = reinterpret_cast<uint32_t *>(nam_lds + 4 * (size_t)n_names);  // [16][n_names]: the histogram
+  if constexpr (LDS) {
+    for (uint32_t i = threadIdx.x; i < 4 * n_names; i += kNamBlock) l64[i] = 0;
+    for (uint32_t i = threadIdx.x; i < BJX_NAMES_HIST * n_names; i += kNamBlock) l32[i] = 0;
+  }
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  unsigned long long n = 0;
+  constexpr uint64_t kTile = (uint64_t)kNamBlock * kNamItems;
+  for (uint64_t base = (uint64_t)blockIdx.x * kTile; base < st_cap; base += (uint64_t)gridDim.x * kTile) {
+    StSlot v[kNamItems];
+#pragma unroll
+    for (int j = 0; j < kNamItems; ++j) {
+      const uint64_t i = base + (uint64_t)j * kNamBlock + threadIdx.x;
+      v[j] = i < st_cap ? st[i] : StSlot{0, 0, 0, 0};  // (an empty slot never passes)
+    }
+#pragma unroll
+    for (int j = 0; j < kNamItems; ++j) {
+      if (!rm_selected(v[j], F, n_ips, n_names, sel)) continue;  // (its IP id is below n_ips, its name id below n_names)
+      keep[(v[j].key >> 24) - 1] = 1u;                          // every writer stores the same value
+      const uint32_t name = (uint32_t)(v[j].key & 0xFFFFFFull);
+      const uint32_t b = bjx_names::bucket(v[j].hits);
+      const unsigned long long kh = bjx_names::key_of(v[j].hits), ks = bjx_names::key_of(v[j].start);
+      if constexpr (LDS) {
+        atomicAdd(&l32[b * n_names + name], 1u);
+        atomicAdd(&l64[name], (unsigned long long)v[j].hits);
+        nam_max(&l64[n_names + name], kh);
+        nam_max(&l64[2 * n_names + name], ks);
+        nam_max(&l64[3 * n_names + name], ~ks);
+      } else {
+        bjx_names::Rec *r = &g[name];
+        atomicAdd((unsigned long long *)&r->hist[b], 1ull);
+        atomicAdd((unsigned long long *)&r->hits, (unsigned long long)v[j].hits);
+        nam_max((unsigned long long *)&r->max_hits, kh);
+        nam_max((unsigned long long *)&r->newest, ks);
+        nam_max((unsigned long long *)&r->oldest_inv, ~ks);
+      }
+      ++n;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d);
+  if ((threadIdx.x & 63) == 0 && n) atomicAdd(&s_n, n);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_n) atomicAdd(&tot[0], s_n);
+  if constexpr (LDS) {
+    for (uint32_t i = threadIdx.x; i < n_names; i += kNamBlock) {
+      bool any = false;
+#pragma unroll
+      for (int b = 0; b < BJX_NAMES_HIST; ++b) {
+        const uint32_t c = l32[b * n_names + i];
+        if (c) {
+          atomicAdd((unsigned long long *)&g[i].hist[b], (unsigned long long)c);
+          any = true;
+        }
+      }
+      if (!any) continue;
+      if (l64[i]) atomicAdd((unsigned long long *)&g[i].hits, l64[i]);
+      atomicMax((unsigned long long *)&g[i].max_hits, l64[n_names + i]);
+      atomicMax((unsigned long long *)&g[i].newest, l64[2 * n_names + i]);
+      atomicMax((unsigned long long *)&g[i].oldest_inv, l64[3 * n_names + i]);
+    }
+  }
+}
+
+// One lane per interned name; every block runs the same number of passes
+// (block_alloc).  A name with a count gets entry k of out[]: its record with
+// n_states = the sum of its bins and its id.  ctr[1] += entries.
+__global__ __launch_bounds__(kBlock) void k_nam_compact(uint32_t n_names, const bjx_names::Rec *__restrict__ g, uint64_t room,
+                                                        unsigned long long *__restrict__ ctr, bjx_names::Rec *__restrict__ out) {
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n_names; base += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t id = base + threadIdx.x;
+    uint64_t cnt = 0;
+    if (id < n_names) {
+#pragma unroll
+      for (int b = 0; b < BJX_NAMES_HIST; ++b) cnt += g[id].hist[b];
+    }
+    const uint64_t k = block_alloc(&ctr[1], cnt ? 1 : 0);
+    if (cnt && k < room) {  // the record is copied only for a name in use
+      out[k] = g[id];
+      out[k].n_states = cnt;
+      out[k].id = (uint32_t)id;
+      out[k]._pad = 0;
+    }
+  }
+}
+
+// The query (the engine lock held by the caller's guarded()).  list == NULL:
+// the rows into e->nam_rows / e->nam_bytes and *out.  list != NULL (the
+// node): every name with a selected state into *list, at most `room` of them,
+// and the counts into *cnt.
+int names_locked(bjx_engine *e, const bjx_state_filter *f, const bjx_names_spec *s, bjx_state_names *out, uint64_t room,
+                 std::vector<bjx_names::Item> *list, bjx_names::Counts *cnt) {
+  const std::string who = "bjx_state_query_names";
+  if (out) memset(out, 0, sizeof *out);
+  if (list) list->clear();
+  if (cnt) *cnt = bjx_names::Counts{};
+  if (const char *why = bjx_names::check_filter(f)) throw BjxError(BJX_ERR_ARG, who + ": " + why);
+  if (const char *why = bjx_names::check_spec(s)) throw BjxError(BJX_ERR_ARG, who + ": " + why);
+  if (e->batch_open) throw BjxError(BJX_ERR_ARG, who + " between bjx_match_batch and its bjx_finish_batch");
+  HIP_OK(hipDeviceSynchronize());  // the tables as the last batch left them
+  State &S = e->S;
+  hipStream_t st = e->stream;
+  SnapEvents E;
+  E.create();
+  read_counters(e);
+  const uint64_t n_ips = e->host_counters[0], used = e->host_counters[1], n_st = e->host_counters[2];
+  const uint32_t n_names = (uint32_t)e->names.size();
+  e->nam_path = 0;
+  if (!list) {
+    e->nam_rows.clear();
+    e->nam_bytes.clear();
+  }
+  QFilter F{f->min_hits, f->min_start_ns, f->max_start_ns, kNone, 0u};
+  if (f->name.ptr) {
+    auto it = e->name_ids.find(std::string(f->name.ptr, f->name.len));
+    if (it == e->name_ids.end()) return BJX_OK;  // never interned: no state can carry it
+    F.name = it->second;
+  }
+  if (bjx_query::empty_window(*f) || !n_ips || !n_st || !n_names) return BJX_OK;
+  if (n_ips >= 0x7FFFFFFFull) throw BjxError(BJX_ERR_CAPACITY, who + ": 2^31 distinct IPs or more");
+  bjx_remove::List L;  // the filter's ip as a list of one (k_rm_ips finds it)
+  bjx_remove::pack(*f, nullptr, 0, &L);
+
+  // every buffer, before anything is launched: all sizes are known now
+  ExpAlloc tmp;
+  bjx_names::Rec *d_acc = tmp.get<bjx_names::Rec>(n_names), *d_out = tmp.get<bjx_names::Rec>(n_names);
+  uint32_t *keep = tmp.get<uint32_t>(n_ips + 1);
+  uint32_t *d_sum = tmp.get<uint32_t>(4);
+  unsigned long long *d_ctr = tmp.get<unsigned long long>(8);  // [0] matched [1] names with a count
+  uint32_t *sel = L.restrict ? tmp.get<uint32_t>(n_ips + 1) : nullptr;
+  const uint64_t off_bytes = ((uint64_t)L.n_entries() + 1) * 4;
+  const uint64_t list_bytes = L.restrict ? off_bytes + L.bytes.size() : 0;
+  uint8_t *d_list = L.restrict ? tmp.get<uint8_t>(((list_bytes + 3) & ~3ull) + 16) : nullptr;
+  if (tmp.nomem) throw BjxError(BJX_ERR_NOMEM, who + ": no device memory for the per-name records");
+  {  // and the sum's scratch, so that cub_call below finds it in place
+    size_t b = 0;
+    HIP_OK(hipcub::DeviceReduce::Sum((void *)nullptr, b, keep, d_sum, (int)n_ips, st));
+    e->cub_tmp.ensure(b + 16);
+  }
+  if (L.restrict) {
+    std::vector<uint8_t> img(list_bytes);
+    memcpy(img.data(), L.off.data(), off_bytes);
+    if (!L.bytes.empty()) memcpy(img.data() + off_bytes, L.bytes.data(), L.bytes.size());
+    snap_copy_in(e, d_list, img.data(), list_bytes);  // one upload; waits for the stream
+  }
+
+  // the path and the grid.  The LDS bins are u32: one block must walk fewer
+  // than 2^32 slots, so the grid never falls below st_cap / 2^32 + 1 blocks
+  // (one block, whatever the cap, up to a table of 2^32 slots = 128 GiB).
+  const uint32_t lds_names = e->dbg_nam_lds_names ? std::min(e->dbg_nam_lds_names, kNamLdsNames) : kNamLdsNames;
+  const bool lds = n_names <= lds_names;
+  const uint64_t tiles = (e->st_cap + (uint64_t)kNamBlock * kNamItems - 1) / ((uint64_t)kNamBlock * kNamItems);
+  uint64_t cap = e->dbg_nam_blocks ? e->dbg_nam_blocks : (lds ? kNamGridLds : kNamGridGlobal);
+  cap = std::max<uint64_t>(cap, (e->st_cap >> 32) + 1);
+  const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, cap));
+  const uint32_t lds_bytes = lds ? n_names * kNamLdsBytes : 0;
+  if (lds && lds_bytes > 64 * 1024 && lds_bytes > e->nam_lds_set) {  // past the 64 KB of dynamic LDS a kernel has by default
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nam_scan<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)kNamLdsMax));
+    e->nam_lds_set = kNamLdsMax;
+  }
+
+  HIP_OK(hipEventRecord(E.ev[0], st));
+  HIP_OK(hipMemsetAsync(d_ctr, 0, 64, st));
+  HIP_OK(hipMemsetAsync(d_sum, 0, 16, st));
+  HIP_OK(hipMemsetAsync(d_acc, 0, (size_t)n_names * sizeof(bjx_names::Rec), st));
+  HIP_OK(hipMemsetAsync(keep, 0, (n_ips + 1) * 4, st));
+  if (L.restrict) {
+    HIP_OK(hipMemsetAsync(sel, 0, (n_ips + 1) * 4, st));
+    hipLaunchKernelGGL(k_rm_ips, dim3(grid_for(L.sel_count)), dim3(kBlock), 0, st, L.sel_first, L.sel_count,
+                       reinterpret_cast<const uint32_t *>(d_list), d_list + off_bytes, e->dbg_hash_mask, S.ip, S.ip_mask, n_ips, S.ip_off,
+                       S.ip_len, S.arena, used, sel);
+    HIP_OK(hipGetLastError());
+  }
+  if (lds)
+    hipLaunchKernelGGL(k_nam_scan<true>, dim3(grid), dim3(kNamBlock), lds_bytes, st, e->st_cap, S.st, F, n_ips, n_names, sel, keep, d_acc,
+                       d_ctr);
+  else
+    hipLaunchKernelGGL(k_nam_scan<false>, dim3(grid), dim3(kNamBlock), 0, st, e->st_cap, S.st, F, n_ips, n_names, sel, keep, d_acc, d_ctr);
+  HIP_OK(hipGetLastError());
+  e->nam_path = lds ? 1 : 2;
+  cub_call(e, [&](void *t, size_t &b) { return hipcub::DeviceReduce::Sum(t, b, keep, d_sum, (int)n_ips, st); });
+  hipLaunchKernelGGL(k_nam_compact, dim3((unsigned)std::min<uint64_t>(grid_for(n_names), 1024)), dim3(kBlock), 0, st, n_names, d_acc,
+                     (uint64_t)n_names, d_ctr, d_out);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord(E.ev[1], st));
+  unsigned long long got[2] = {0, 0};
+  uint32_t ips_matched = 0;
+  pin_get(e, got, d_ctr, 16);
+  pin_get(e, &ips_matched, d_sum, 4);
+  pin_sync(e);
+  const double ms = E.ms(0, 1);
+  const uint64_t matched = got[0], n_used = got[1];
+  if (matched > n_st || n_used > n_names || n_used > matched || ips_matched > matched || (matched != 0) != (n_used != 0))
+    throw BjxError(BJX_ERR_DEVICE, "internal: names counts disagree with the tables");
+  if (list && n_used > room) throw BjxError(BJX_ERR_CAPACITY, who + ": more names than the node merges");
+  std::vector<bjx_names::Rec> recs(n_used);
+  if (n_used) {
+    HIP_OK(hipMemcpyAsync(recs.data(), d_out, n_used * sizeof(bjx_names::Rec), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+  }
+  uint64_t sum = 0;
+  std::vector<bjx_names::Item> items(n_used);
+  for (uint64_t k = 0; k < n_used; ++k) {
+    if (recs[k].id >= n_names) throw BjxError(BJX_ERR_DEVICE, "internal: names records disagree with the interned names");
+    items[k].name = e->names[recs[k].id];
+    items[k].r = recs[k];
+    sum += recs[k].n_states;
+  }
+  if (sum != matched) throw BjxError(BJX_ERR_DEVICE, "internal: names records do not add up to the matched states");
+  bjx_names::Counts C;
+  C.n_matched = matched;
+  C.n_ips_matched = ips_matched;
+  C.device_ms = ms;
+  if (list) {
+    *list = std::move(items);
+    *cnt = C;
+    return BJX_OK;
+  }
+  bjx_names::finish(std::move(items), *s, C, out, &e->nam_rows, &e->nam_bytes);
+  return BJX_OK;
+}
+
+}  // namespace
+
+// test hooks (include/banjax_gpu_debug.h)
+extern "C" int bjx_debug_set_names(bjx_engine *e, uint32_t max_lds_names, uint32_t max_blocks) {
+  if (!e) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->dbg_nam_lds_names = max_lds_names;
+  e->dbg_nam_blocks = max_blocks;
+  return BJX_OK;
+}
+extern "C" int bjx_debug_names_info(bjx_engine *e, int *path, uint32_t *lds_names_max) {
+  if (!e) return BJX_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  if (path) *path = e->nam_path;
+  if (lds_names_max) *lds_names_max = kNamLdsNames;
+  return BJX_OK;
+}
+
+extern "C" int bjx_state_query_names(bjx_engine *e, const bjx_state_filter *f, const bjx_names_spec *s, bjx_state_names *out) {
+  if (!e || !f || !s || !out) return BJX_ERR_ARG;
+  return guarded(e, [&]() -> int { return names_locked(e, f, s, out, 0, nullptr, nullptr); });
+}
+
+int bjx_names_list(bjx_engine *e, const bjx_state_filter *f, const bjx_names_spec *s, uint64_t room,
+                   std::vector<bjx_names::Item> *list, bjx_names::Counts *counts) {
+  if (!e || !f || !s || !list || !counts) return BJX_ERR_ARG;
+  return guarded(e, [&]() -> int { return names_locked(e, f, s, nullptr, room, list, counts); });
+}

@@ -559,6 +559,52 @@ class Engine:
         ans["rows"] = rows
         return ans
 
+    _names = "bjx_state_query_names"
+
+    def state_query_names(self, order=_lib.NAMES_BY_STATES, limit: int = 100, min_states: int = 0, ip=None, name=None,
+                          min_hits: int = INT64_MIN, min_start_ns: int = INT64_MIN, max_start_ns: int = INT64_MAX) -> dict:
+        """Which rule names hold the state: the states that pass the filter
+        (state_query's ip, name, min_hits, min_start_ns, max_start_ns) totalled
+        per rule name (bjx_state_query_names; banjax_amd/state_names.py
+        documents the totals, the histogram buckets and the order and is its
+        model).  order: _lib.NAMES_BY_STATES, _BY_HITS, _BY_MAX_HITS,
+        _BY_NEWEST or _BY_NAME (or "states" / "hits" / "max_hits" / "newest" /
+        "name"); rows only for names of at least min_states states; limit 0:
+        the counts only.  Returns {"n_matched", "n_ips_matched", "n_names",
+        "n_names_min", "rows": [state_names.NameRow], "device_ms"}; a row's
+        .name is bytes, what state_remove(name=...) takes.  After a reload,
+        state_names.orphans(rows, current rule names) are the rows to remove.
+        The engine is unchanged."""
+        from .state_names import ORDERS, NameRow
+        order = ORDERS.get(order, order)
+        ipb = None if ip is None else _lib.b(ip)
+        nb = None if name is None else _lib.b(name)
+        f = _lib.StateFilter(_lib.Str(ipb, len(ipb or b"")), _lib.Str(nb, len(nb or b"")), min_hits, min_start_ns,
+                             max_start_ns, _lib.QUERY_BY_HITS, 0)
+        s = _lib.NamesSpec(order, limit, min_states)
+        out = _lib.StateNames()
+        self._check(getattr(_lib.lib(), self._names)(self._h, C.byref(f), C.byref(s), C.byref(out)), "state_query_names")
+        blob = C.string_at(out.bytes, out.n_bytes) if out.n_bytes else b""
+        rows = []
+        for k in range(out.n_rows):
+            r = out.rows[k]
+            rows.append(NameRow(blob[r.name_off:r.name_off + r.name_len], r.n_states, r.hits_sum, r.max_hits,
+                                r.newest_start_ns, r.oldest_start_ns, tuple(r.hist)))
+        ans = {k: getattr(out, k) for k in ("n_matched", "n_ips_matched", "n_names", "n_names_min", "device_ms")}
+        ans["rows"] = rows
+        return ans
+
+    def debug_set_names(self, max_lds_names: int = 0, max_blocks: int = 0):
+        """Test hook: state_query_names bins in LDS only up to max_lds_names interned names and
+        scans with at most max_blocks blocks (0 = default)."""
+        self._check(_lib.lib().bjx_debug_set_names(self._h, max_lds_names, max_blocks), "debug_set_names")
+
+    def debug_names_info(self):
+        """-> (where the last state_query_names binned: "none" / "lds" / "global", the most interned names the LDS path takes)"""
+        path, top = C.c_int(0), C.c_uint32(0)
+        self._check(_lib.lib().bjx_debug_names_info(self._h, C.byref(path), C.byref(top)), "debug_names_info")
+        return {0: "none", 1: "lds", 2: "global"}[path.value], top.value
+
     def debug_set_trim_grid(self, max_blocks: int):
         """Test hook: the block cap of state_trim's counting passes (0 = default)."""
         self._check(_lib.lib().bjx_debug_set_trim_grid(self._h, max_blocks), "debug_set_trim_grid")
@@ -740,6 +786,9 @@ class Node:
 
     _groups = "bjx_node_state_query_groups"
     state_query_groups = Engine.state_query_groups  # the shards' complete group lists merged by key, then min_ips, order, limit
+
+    _names = "bjx_node_state_query_names"
+    state_query_names = Engine.state_query_names  # the shards' complete name lists merged by name bytes, then min_states, order, limit
 
     _rule_stats = "bjx_node_"
     rule_stats = Engine.rule_stats  # the engines' arrays summed; engine(k).rule_stats() has engine k's own

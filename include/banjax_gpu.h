@@ -792,6 +792,94 @@ typedef struct bjx_state_groups {   /* 72 B */
   double device_ms;       /* HIP events, copies excluded */
 } bjx_state_groups;
 int bjx_state_query_groups(bjx_engine *e, const bjx_state_filter *f, const bjx_group_spec *g, bjx_state_groups *out);
+/* ---- Names: which rule names hold the state.  State is keyed by IP bytes
+   and rule name and survives ruleset swaps, so after a reload that renames,
+   drops or retunes rules the engine still keeps every state of the old names.
+   bjx_state_remove and bjx_state_query act on a name once somebody gives it;
+   this call lists the names: one pass over the state table, aggregated per
+   name on the device, and a small answer.
+
+   Selection: a state is selected when it has valid != 0 and passes the five
+   conditions of *f exactly as bjx_state_query reads them (ip, name, min_hits,
+   min_start_ns, max_start_ns).  f->order and f->limit change nothing in the
+   answer (a filter bjx_state_query refuses is still refused).  f->ip is
+   honoured as the groups call honours it (the names that IP holds; the table
+   is still read once, there is no scan-free path); f->name set gives at most
+   one row.
+
+   Rows: a name without a selected state has no row, however it came to be
+   interned (a bound ruleset whose rule never matched, a claim that was refused
+   or undone, a removal since).  The names with n_states >= min_states are
+   ordered by the primary key descending -- n_states, hits_sum (as signed
+   int64), max_hits or newest_start_ns; BJX_NAMES_BY_NAME has no primary key --
+   then by name bytewise ascending, a prefix before the longer name; the first
+   `limit` of them.  The order is total and a function of the logical state
+   alone: slot layout, table sizes, name ids, the order the names were
+   interned in and the debug hash mask do not show.  A row's name is
+   bytes[name_off, name_off + name_len).  hits_sum wraps as Go's int addition
+   does.  hist counts the row's states by hits: bucket 0 hits <= 0, bucket b
+   (1..14) the hits of bit length b, 2^(b-1) <= hits < 2^b, bucket 15 hits >=
+   2^14.  Over all names the n_states add up to n_matched; for every row
+   sum(hist) == n_states.
+
+   Against the other calls, for every row: bjx_state_query with the same *f
+   and name = the row's name reports n_matched == n_ips_matched == n_states
+   ((ip, name) is unique), its top row by hits carries max_hits and by start
+   newest_start_ns; with min_hits = 2^k added (k = 0..14, f->min_hits <= 2^k)
+   it reports hist[k+1] + ... + hist[15]; bjx_state_remove with the same
+   filter and that name reports states_dropped == n_states.
+
+   Not errors (zero rows, zero counts): an engine without state, a name the
+   engine never interned, an empty start window, an IP not held.
+   BJX_ERR_ARG, with the engine unchanged: a NULL handle, f, s or out; an
+   unknown order; limit > BJX_NAMES_MAX_ROWS; what bjx_state_query refuses in
+   *f, and f->ip or f->name with len > 0 and a NULL ptr; a call between
+   bjx_match_batch and its bjx_finish_batch* (the node call waits for the node
+   batch instead).  BJX_ERR_NOMEM: a failed allocation (everything is of known
+   size and allocated before the first launch).  The engine is unchanged in
+   every case: the tables are only read.  rows and bytes are engine-owned and
+   valid until the next names query on the handle.  Takes the engine lock like
+   the other bjx_state_* calls.
+
+   Temporary device memory: two arrays of 176-byte records sized by the names
+   the engine has interned (the accumulators and their compacted copy), 4 bytes
+   per held IP for n_ips_matched, and with f->ip another 4 per held IP; no
+   per-state temporary -- the state table is read in place, once.  What is
+   copied back is proportional to the names in use, not to the names
+   interned.  Cost: while the engine has interned at most 1,365 names (what
+   bjx_debug_names_info reports as lds_names_max) the per-name sums are kept
+   in on-chip memory and the call costs about what a counts-only
+   bjx_state_query costs; past that every selected state adds straight to the
+   per-name records in device memory and the call changes class -- about 170
+   times slower on a state of 55M states under 1,006 names (DESIGN.md §2
+   "Names").  Names stay interned for the life of the engine, so a host that
+   reloads rulesets with ever new names gets there over time. */
+enum bjx_names_order { BJX_NAMES_BY_STATES = 0, BJX_NAMES_BY_HITS = 1, BJX_NAMES_BY_MAX_HITS = 2,
+                       BJX_NAMES_BY_NEWEST = 3, BJX_NAMES_BY_NAME = 4 };
+#define BJX_NAMES_MAX_ROWS 65536
+#define BJX_NAMES_HIST 16
+typedef struct bjx_names_spec {   /* 16 B */
+  uint32_t order;       /* enum bjx_names_order */
+  uint32_t limit;       /* rows wanted, 0..BJX_NAMES_MAX_ROWS; 0: counts only */
+  uint64_t min_states;  /* rows only for names with n_states >= min_states (0 and 1: every name) */
+} bjx_names_spec;
+typedef struct bjx_name_row {     /* 184 B */
+  uint64_t name_off; uint32_t name_len, _pad;   /* into bjx_state_names.bytes */
+  uint64_t n_states;          /* selected states under the name == distinct IPs holding one ((ip, name) is unique) */
+  int64_t hits_sum;           /* wrapping as Go int addition, as bjx_group_row */
+  int64_t max_hits;
+  int64_t newest_start_ns, oldest_start_ns;
+  uint64_t hist[BJX_NAMES_HIST]; /* by hits: bucket 0: hits <= 0; bucket b: bit_length(hits) == b; bucket 15: hits >= 2^14 */
+} bjx_name_row;
+typedef struct bjx_state_names {  /* 72 B */
+  uint64_t n_matched, n_ips_matched;  /* exactly bjx_state_query's for the same *f */
+  uint64_t n_names;       /* distinct names with a selected state */
+  uint64_t n_names_min;   /* those with n_states >= min_states */
+  uint64_t n_rows;        /* min(limit, n_names_min) */
+  const bjx_name_row *rows; const uint8_t *bytes; uint64_t n_bytes;  /* engine-owned (node-owned), valid until the next names query on the handle */
+  double device_ms;       /* HIP events, copies excluded */
+} bjx_state_names;
+int bjx_state_query_names(bjx_engine *e, const bjx_state_filter *f, const bjx_names_spec *s, bjx_state_names *out);
 /* RegexRateLimitStates.String(): "ip:\n\trule:\n\t\t{hits start}\n" blocks, IPs in
    first-seen order.  Returns the full length (writes at most cap bytes). */
 size_t bjx_state_dump(bjx_engine *e, char *out, size_t cap);
@@ -1063,6 +1151,18 @@ int bjx_node_state_trim(bjx_node *n, const bjx_trim_budget *b, bjx_trim_stats *o
    node-owned until the next groups query on the node.  Waits for the node
    batch, as bjx_node_state_expire does. */
 int bjx_node_state_query_groups(bjx_node *n, const bjx_state_filter *f, const bjx_group_spec *g, bjx_state_groups *out);
+/* bjx_state_query_names over the node.  A name's states are spread over the
+   engines (the owner of an IP is a hash of its bytes), so every engine gives
+   the complete list of its names, the host merges the lists by name bytes
+   (counts, hits_sum -- wrapping -- and hist added, max_hits and
+   newest_start_ns the largest, oldest_start_ns the smallest) and only then
+   applies min_states, the order and the limit: no per-shard limit cuts before
+   the merge.  The answer equals one engine over the union of the state.
+   n_matched and n_ips_matched are summed, device_ms is the slowest shard's.
+   When the shards' lists together hold more than 2^20 names the call returns
+   BJX_ERR_CAPACITY.  rows and bytes are node-owned until the next names query
+   on the node.  Waits for the node batch, as bjx_node_state_expire does. */
+int bjx_node_state_query_names(bjx_node *n, const bjx_state_filter *f, const bjx_names_spec *s, bjx_state_names *out);
 /* bjx_batch_rule_stats / bjx_rule_stats_total / bjx_rule_stats_reset over the
    node: the engines' arrays summed (engine k counted chunk k's lines),
    n_lines summed, device_ms the slowest engine's (totals: those summed). */

@@ -92,6 +92,17 @@ int bjx_debug_set_trim_grid(bjx_engine *e, uint32_t max_blocks);
 /* The number of sorted keys one block of bjx_state_query_groups' run reduction
    (k_grp_runs) handles: the tests place group sizes and boundaries around it. */
 uint32_t bjx_debug_groups_tile(void);
+/* Test hook: bjx_state_query_names keeps its per-name bins in LDS only while
+   the engine has interned at most max_lds_names names (0 = default, what the
+   LDS a block may have holds; a larger value changes nothing), and its pass
+   over the state table launches at most max_blocks blocks (0 = the default
+   cap), so that small inputs reach both paths, the exact boundary and one
+   block that walks the whole table. */
+int bjx_debug_set_names(bjx_engine *e, uint32_t max_lds_names, uint32_t max_blocks);
+/* *path: where the engine's last bjx_state_query_names binned: 1 LDS, 2 the
+   global records, 0 nothing was launched.  *lds_names_max: the most interned
+   names the LDS path takes without the hook.  Either may be NULL. */
+int bjx_debug_names_info(bjx_engine *e, int *path, uint32_t *lds_names_max);
 /* Test hook: the state-table slot index each of n (IP, rule name) states
    occupies, found as bjx_state_get finds it (hash, probe chain, IP bytes,
    then the state's key), in one launch for the whole list; -1 where there is
